@@ -11,6 +11,12 @@ times it: compress(frame) + decompress(bytes) of ONE frame, each closed by a dev
 models/convolutional/lossy_coord_v2/model.py:196-205).  Frames are independent, so N GPUs run N replicas on different frames (weak
 scaling, no data-path collective).  Weights: seeded random initialisation of the architecture (no checkpoints exist here); data: seeded
 synthetic voxel surface (fastpcc_amd/synthetic.py).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set-up, --warmup steps, the --steps timed steps, the result line (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  --full adds everything else the benchmark measures or checks, outside the
+timed region as before: the frames coded alone (every timed step must reproduce their streams), `value_one_frame`, the `roofline`
+(per-launch events in the last timed steps, the shader-clock step), D1 / D2 PSNR, the other configurations (`config.secondary`)
+and the CPU oracle (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step returned (rank 0), see dump_outputs().
 """
 import argparse
 import json
@@ -48,8 +54,15 @@ def parse():
     ap.add_argument('--own-streams', type=int, default=0, help='1: every frame in flight on a HIP stream of its own (kernels of different frames overlap)')
     ap.add_argument('--ddp-steps', type=int, default=10, help='optimisation steps of the cfg#5 DDP figure (N > 1)')
     ap.add_argument('--ddp-deadline', type=float, default=420.0, help='seconds after which rank 0 prints the headline without the DDP figure')
-    ap.add_argument('--dump-trace', default='', help='write the per-launch conv table of the last step to this file')
-    return ap.parse_args()
+    ap.add_argument('--dump-trace', default='', help='write the per-launch conv table of the last step to this file (with --full)')
+    ap.add_argument('--full', action='store_true', help='also measure and check what the headline does not need: the frames coded alone '
+                    'and the per-step stream check, value_one_frame, roofline, PSNR, the secondary configurations, the CPU baseline')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR', help='after the timed steps, write what the last one returned on rank 0 '
+                    'as DIR/<name>.npy (see dump_outputs)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
 
 
 def conv_flops(info, counts_cache):
@@ -341,6 +354,44 @@ def secondary(device):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+DUMP_ROWS_PER_CLOUD = 131072
+
+
+def dump_outputs(out_dir, streams, clouds):
+    """What one step returns to its caller -- compress_many's B byte streams and decompress_many's B decoded clouds -- as float32 .npy
+    files, for comparing two builds output for output (same arguments = same inputs):
+        stream_<i>.npy        the bytes of stream i, one value per byte (a seeded sample of its bytes, in order, beyond the budget)
+        decoded_<i>.npy       [k, 3] coordinates of decoded cloud i in lexicographic order (the decoder returns a set of voxels);
+                              k = all rows up to DUMP_ROWS_PER_CLOUD, else a seeded sample of the sorted rows, in order
+        stream_bytes.npy      [B] the length of every stream
+        decoded_points.npy    [B] the number of voxels of every decoded cloud
+    At most DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    B = len(streams)
+
+    def sample(a, rows, seed):
+        if len(a) <= rows:
+            return a
+        return a[np.sort(np.random.default_rng(seed).choice(len(a), rows, replace=False))]
+
+    # half the budget for the streams, the rest for the decoded clouds (the counts are a few bytes)
+    stream_rows = max(1, DUMP_BUDGET_BYTES // 2 // (4 * B))
+    for i, s in enumerate(streams):
+        np.save(os.path.join(out_dir, f'stream_{i:02d}.npy'), sample(np.frombuffer(s, np.uint8), stream_rows, i).astype(np.float32))
+    used = sum(os.path.getsize(os.path.join(out_dir, f'stream_{i:02d}.npy')) for i in range(B))
+    cloud_rows = max(1, min(DUMP_ROWS_PER_CLOUD, (DUMP_BUDGET_BYTES - used - 64 * 1024) // (12 * B)))
+    for i, r in enumerate(clouds):
+        r = r.to(torch.int64)
+        key = (r[:, 0] << 42) | (r[:, 1] << 21) | r[:, 2]
+        rows = r[torch.argsort(key)].cpu().numpy()
+        np.save(os.path.join(out_dir, f'decoded_{i:02d}.npy'), sample(rows, cloud_rows, 1000 + i).astype(np.float32))
+    np.save(os.path.join(out_dir, 'stream_bytes.npy'), np.array([len(s) for s in streams], np.float64))
+    np.save(os.path.join(out_dir, 'decoded_points.npy'), np.array([r.shape[0] for r in clouds], np.float64))
+
+
 def main():
     args = parse()
     if args.cpu_baseline_worker:
@@ -353,7 +404,7 @@ def main():
     # the CPU baseline runs in a child process that is CREATED here, before this process initialises the GPU, and stays idle until
     # the GPU legs are done (cpu_job.result() at the end releases it): its 32 threads must not run beside or right before the timed
     # region, whose two frames in flight are paced by two host threads
-    cpu_job = CpuBaseline(args.cpu_resolution) if (args.cpu_baseline and world == 1 and rank == 0) else None
+    cpu_job = CpuBaseline(args.cpu_resolution) if (args.full and args.cpu_baseline and world == 1 and rank == 0) else None
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -386,7 +437,10 @@ def main():
 
     # every rank codes its own frames (different seeds), all ~1M voxels: B = --batch of them per step
     B = max(1, args.batch)
-    clouds = [body_cloud(args.resolution, SCALE.get(args.resolution, 1.0), seed=2 + rank * B + i) for i in range(B)]
+    # ~2 s of NumPy per cloud, most of it outside the GIL: generated on a few threads (each cloud from its own seed, so the same clouds)
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max_workers=min(B, 8)) as ex:
+        clouds = list(ex.map(lambda i: body_cloud(args.resolution, SCALE.get(args.resolution, 1.0), seed=2 + rank * B + i), range(B)))
     frames = [torch.from_numpy(batched(c)).cuda() for c in clouds]
     frame, xyz = frames[0], clouds[0]
     n_points = frame.shape[0]
@@ -416,25 +470,27 @@ def main():
         ME.clear_global_coordinate_manager()
         return data, rec, b - a, c - b
 
-    # reference results of every frame, coded alone: what every step of the timed region must reproduce byte for byte
-    want_bytes, want_points = [], []
-    for f in frames:
-        data, rec, _, _ = one_frame(f)
-        # the decoder keeps the candidates above the (8M - N)-th smallest logit; logits that tie with that threshold are
-        # dropped, exactly as in the reference (lossy_coord_v2/layers.py:164-180), so the count can fall short by the ties
-        assert f.shape[0] - max(16, f.shape[0] // 1000) <= rec.shape[0] <= f.shape[0], (rec.shape[0], f.shape[0])
-        want_bytes.append(data)
-        want_points.append(rec.shape[0])
+    want_bytes = want_points = None
+    if args.full:
+        # reference results of every frame, coded alone: what every step of the timed region must reproduce byte for byte
+        want_bytes, want_points = [], []
+        for f in frames:
+            data, rec, _, _ = one_frame(f)
+            # the decoder keeps the candidates above the (8M - N)-th smallest logit; logits that tie with that threshold are
+            # dropped, exactly as in the reference (lossy_coord_v2/layers.py:164-180), so the count can fall short by the ties
+            assert f.shape[0] - max(16, f.shape[0] // 1000) <= rec.shape[0] <= f.shape[0], (rec.shape[0], f.shape[0])
+            want_bytes.append(data)
+            want_points.append(rec.shape[0])
 
-    # The metric by its BASELINE definition (the reference's Timer blocks, lossy_coord_v2/model.py:196-205): N0 / (t_enc + t_dec),
-    # one frame at a time, each half closed by a device synchronise -- median over `--latency-frames` frames (>= 10) after 2 warm-ups.
-    for _ in range(2):
-        one_frame(frame)
-    lat = [one_frame(frame)[2:] for _ in range(max(1, args.latency_frames))]
-    enc_ms = statistics.median(t[0] for t in lat) * 1e3
-    dec_ms = statistics.median(t[1] for t in lat) * 1e3
-    one_frame_ms = statistics.median(t[0] + t[1] for t in lat) * 1e3
-    value_one_frame = n_points / one_frame_ms / 1e3
+        # The metric by its BASELINE definition (the reference's Timer blocks, lossy_coord_v2/model.py:196-205): N0 / (t_enc + t_dec),
+        # one frame at a time, each half closed by a device synchronise -- median over `--latency-frames` frames (>= 10) after 2 warm-ups.
+        for _ in range(2):
+            one_frame(frame)
+        lat = [one_frame(frame)[2:] for _ in range(max(1, args.latency_frames))]
+        enc_ms = statistics.median(t[0] for t in lat) * 1e3
+        dec_ms = statistics.median(t[1] for t in lat) * 1e3
+        one_frame_ms = statistics.median(t[0] + t[1] for t in lat) * 1e3
+        value_one_frame = n_points / one_frame_ms / 1e3
 
     import contextlib
     use_stages = args.stages == 1 or (args.stages < 0 and B < 4)
@@ -448,8 +504,8 @@ def main():
             rec = ctx_model.decompress_many(data)
             wait_for_my_work(device)                     # this batch's last kernel, not the other batch's queue
             ME.clear_global_coordinate_manager()
-        # every step, inside the timed region: the streams are the single-frame streams, the decoders returned the coded points
-        if data != want_bytes or [r.shape[0] for r in rec] != want_points:
+        # every step, inside the timed region (--full): the streams are the single-frame streams, the decoders returned the coded points
+        if want_bytes is not None and (data != want_bytes or [r.shape[0] for r in rec] != want_points):
             raise RuntimeError('a step of the timed region did not reproduce the frames\' own streams / point counts')
         return data, rec
 
@@ -460,20 +516,22 @@ def main():
         replicas.barrier(device)
 
     # Per-launch HIP events around every convolution cost ~6 us apiece (~1 ms a step now), so they are recorded on the last
-    # THREE steps of the timed region (one step when fewer than 10 are timed); `roofline` is the mean over their launches.
-    trace_steps = 3 if args.steps >= 10 else 1
+    # THREE steps of the timed region (one step when fewer than 10 are timed); `roofline` is the mean over their launches.  --full only.
+    trace_steps = (3 if args.steps >= 10 else 1) if args.full else 0
     # a serving process does this once its models are loaded: everything allocated so far leaves the cyclic collector's
     # generations, so the collections that do run between frames only scan what the frames themselves left behind
     import gc
     gc.collect()
     gc.freeze()
-    hipops.reserve_trace_events(600 * trace_steps)         # before the timed region: the traced steps only record
-    # The shader clock the step actually gets: beside every large 3x3x3 launch of ONE EXTRA step after the timed region a one-wave kernel on a second
-    # stream counts shader cycles against the constant 100 MHz counter for 100 us (fpcc_clock_probe).  MI355X's power management
-    # starts a burst of matrix work near 2.0 GHz and takes ~30 ms of uninterrupted load to reach the 2.4 GHz the peak is quoted at
-    # (profiles/r03/clock_ramp.md); a step with host-paced gaps never gets there.
-    clock_stream = torch.cuda.Stream(device=device)
-    clock_buf = torch.zeros((64, 2), dtype=torch.int64, device=device)
+    if trace_steps:
+        hipops.reserve_trace_events(600 * trace_steps)     # before the timed region: the traced steps only record
+    # The shader clock the step actually gets (--full): beside every large 3x3x3 launch of ONE EXTRA step after the timed region a
+    # one-wave kernel on a second stream counts shader cycles against the constant 100 MHz counter for 100 us (fpcc_clock_probe).
+    # MI355X's power management starts a burst of matrix work near 2.0 GHz and takes ~30 ms of uninterrupted load to reach the 2.4 GHz
+    # the peak is quoted at (profiles/r03/clock_ramp.md); a step with host-paced gaps never gets there.
+    if args.full:
+        clock_stream = torch.cuda.Stream(device=device)
+        clock_buf = torch.zeros((64, 2), dtype=torch.int64, device=device)
     clock_idx = []
 
     def clock_hook(ev0, n_out, n_offsets):
@@ -508,7 +566,9 @@ def main():
     results = pipeline.map(timed_step, range(args.steps))
     barrier()
     elapsed = time.perf_counter() - t0
-    hbm_peak_gib = torch.cuda.max_memory_allocated(device) / 2 ** 30          # reference frames, warm-up and the timed region
+    hbm_peak_gib = torch.cuda.max_memory_allocated(device) / 2 ** 30          # (reference frames,) warm-up and the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, results[-1][0], results[-1][1])
     data, rec = results[-1][0][0], results[-1][1][0]
     del results
     if os.environ.get('FPCC_BENCH_STEP_TIMES') == '1':
@@ -518,37 +578,66 @@ def main():
     pipeline.close()
     del pipeline
     trace, hipops.CONV_TRACE = hipops.CONV_TRACE, None
-    # one more frame, outside the timed region and outside `roofline`'s events, for the clock: the probe kernel beside a launch
-    # disturbs that launch's own timing (+15 % on the traced kernel time when both were taken in the same steps)
-    hipops.reserve_trace_events(600)
-    hipops.CONV_TRACE, hipops.CLOCK_HOOK = [], clock_hook
-    if B > 1:                                            # the clock of the workload the timed region ran: one batch, alone
-        extra = model.compress_many(frames)
-        torch.cuda.synchronize()
-        ME.clear_global_coordinate_manager()
-        model.decompress_many(extra)
-        torch.cuda.synchronize()
-        ME.clear_global_coordinate_manager()
-        del extra
-    else:
-        one_frame(frame)
-    clock_trace, hipops.CONV_TRACE, hipops.CLOCK_HOOK = hipops.CONV_TRACE, None, None
+    if args.full:
+        # one more frame, outside the timed region and outside `roofline`'s events, for the clock: the probe kernel beside a launch
+        # disturbs that launch's own timing (+15 % on the traced kernel time when both were taken in the same steps)
+        hipops.reserve_trace_events(600)
+        hipops.CONV_TRACE, hipops.CLOCK_HOOK = [], clock_hook
+        if B > 1:                                        # the clock of the workload the timed region ran: one batch, alone
+            extra = model.compress_many(frames)
+            torch.cuda.synchronize()
+            ME.clear_global_coordinate_manager()
+            model.decompress_many(extra)
+            torch.cuda.synchronize()
+            ME.clear_global_coordinate_manager()
+            del extra
+        else:
+            one_frame(frame)
+        clock_trace, hipops.CONV_TRACE, hipops.CLOCK_HOOK = hipops.CONV_TRACE, None, None
 
     elapsed_max, total_points = replicas.aggregate(elapsed, float(points_per_step) * args.steps, device)
     # self-validation of an N-rank run: ranks counted by an all-reduce of ones on the device, every rank's own throughput min / max
     spread = replicas.rank_spread(points_per_step * args.steps / elapsed / 1e6, device)
-    spread_one = replicas.rank_spread(value_one_frame, device)
-
-    # rate / distortion of the frame just coded (outside the timed region): bpp and D1-PSNR as the reference's evaluator
-    # reports them, distortion computed on the device (fastpcc_amd/evaluators.py)
-    # (point-to-point and point-to-plane lines of pc_error; normals estimated on the device as the reference does with Open3D when
-    # the PLY carries none -- 14 ms for the 1 M-voxel pair, profiles/r06/README.md)
-    from fastpcc_amd.evaluators import pc_error_metrics
-    quality = pc_error_metrics(frame[:, 1:], rec, args.resolution)
+    if args.full:
+        spread_one = replicas.rank_spread(value_one_frame, device)
+        # rate / distortion of the frame just coded (outside the timed region): bpp and D1-PSNR as the reference's evaluator
+        # reports them, distortion computed on the device (fastpcc_amd/evaluators.py)
+        # (point-to-point and point-to-plane lines of pc_error; normals estimated on the device as the reference does with Open3D when
+        # the PLY carries none -- 14 ms for the 1 M-voxel pair, profiles/r06/README.md)
+        from fastpcc_amd.evaluators import pc_error_metrics
+        quality = pc_error_metrics(frame[:, 1:], rec, args.resolution)
 
     n_bytes = len(data)
     out = None
-    if rank == 0:
+    if rank == 0 and not args.full:
+        out = {
+            'metric': f'encode+decode Mpoints/sec, lossy_coord_v2 baseline_r1 (stream of {B}-frame batches, {depth} in flight; '
+                      'one frame at a time = value_one_frame)',
+            'value': round(total_points / elapsed_max / 1e6, 4),
+            'unit': 'Mpoints/s',
+            'value_batched': round(total_points / elapsed_max / 1e6, 4),
+            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'rccl_ranks': spread['ranks'], 'collective_backend': spread['backend'],
+            'per_rank_value': {'min': round(spread['min'], 4), 'max': round(spread['max'], 4)},
+            'ms_per_step': round(elapsed_max / args.steps * 1e3, 3),
+            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+            'dtype': 'f32', 'data': 'synthetic',
+            'config': {'workload': f'lossy_coord_v2/baseline_r1 inference, {n_points}-voxel {args.resolution}^3 '
+                                   f'body-surface frames (cfg#2), seeded random-init weights; one step = a batch of {B} such frames per GPU '
+                                   f'({points_per_step} voxels) through compress_many + decompress_many = ONE network traversal over the batch, '
+                                   f'{B} independent streams; {depth} batch(es) in flight per GPU',
+                       'parallelism': (f'replicas x{world} (independent frames)' if world > 1 else 'single GPU') +
+                                      (f', {depth} batches in flight per GPU on one stream (fastpcc_amd/serving.py)' if depth > 1 else ''),
+                       'batch_clouds': B, 'frames_in_flight': depth, 'named_stages': bool(use_stages), 'voxels_per_step': points_per_step,
+                       'value_note': 'value = steps x voxels_per_step / elapsed of the whole timed region (throughput of a stream of frames); '
+                                     'value_one_frame, the stream check against the frames coded alone, roofline, PSNR, the secondary '
+                                     'configurations and the CPU baseline: bench.py --full',
+                       'bytes': n_bytes, 'bpp': round(8 * n_bytes / n_points, 4),
+                       'coder_handover_retries': GeoLosslessEntropyModel.handover_retries,
+                       'hbm_peak_gib': round(hbm_peak_gib, 1),
+                       'host_binding': numa if numa is not None else 'none'},
+        }
+    if rank == 0 and args.full:
         # dominant kernel: the MFMA sparse convolution.  algorithmic flop / measured duration of its launches
         cache = {}
         flops = ms = bytes_fused = 0.0
@@ -660,7 +749,7 @@ def main():
     # prints the record and ends the job with a non-zero code instead of losing the measurement (the process group's own
     # timeout, 5 minutes, would otherwise be the only way out).
     failed = False
-    if args.secondary and world > 1:
+    if args.full and args.secondary and world > 1:
         watchdog = None
         if rank == 0:
             import threading
@@ -688,7 +777,7 @@ def main():
             out['config']['secondary'] = {'cfg5_training_ddp': ddp_record}
             failed = failed or (ddp_record is not None and 'error' in ddp_record)
     if rank == 0:
-        if args.secondary and world == 1:
+        if args.full and args.secondary and world == 1:
             del model, frame, frames
             out['config']['secondary'] = secondary(device)
         if cpu_job is not None:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rolls the per-launch table of `bench.py --dump-trace` (ONE traced step) up by map size and kernel shape.
+"""Rolls the per-launch table of `bench.py --full --dump-trace` (ONE traced step) up by map size and kernel shape.
 
     python profiles/conv_by_level.py <conv_launches.txt> > profiles/rNN/<tag>_conv_by_level.md"""
 import collections
@@ -27,7 +27,7 @@ def main(path):
             e[1] += float(ms)
             e[2] += float(gflop)
     print(f'# MFMA convolution launches of the default bench run, by map size and kernel shape: ONE of the traced steps')
-    print(f'# source: {path} (bench.py --dump-trace, the last traced step); peak {PEAK} TFLOP/s at the nominal 2.4 GHz; event-timed (includes launch gaps)')
+    print(f'# source: {path} (bench.py --full --dump-trace, the last traced step); peak {PEAK} TFLOP/s at the nominal 2.4 GHz; event-timed (includes launch gaps)')
     print('| rows of the map | kernel | launches | ms / step | algorithmic GFLOP | TFLOP/s | fraction of peak |')
     print('|---|---|---:|---:|---:|---:|---:|')
     tot = [0, 0.0, 0.0]

@@ -9,6 +9,7 @@ Sources of truth used:
                  overflow coding, with/without indexes), BinaryRansCoder, simple RansEncoder; plus
                  batched_pmf_to_quantized_cdf incl. the known-answer assertion of
                  /root/reference/lib/entropy_models/rans_coder/__init__.py:72-77
+  rans_random.json  the same BinaryRansCoder / IndexedRansCoder on ten seeded random streams: inputs and the streams written
   morton.json    /root/reference/lib/space_filling_curves/__init__.py:65-88 (CPU path, imported with the CUDA loader stubbed)
   byteslist.json /root/reference/lib/entropy_models/hyperprior/noisy_deep_factorized/utils.py:8-77
   entropy_model.json  NoisyDeepFactorizedEntropyModel of /root/reference/lib/entropy_models/continuous_batched.py
@@ -149,6 +150,28 @@ def make_rans():
     e.encode_bin(edge, bits)
     out['simple'].append({'bin': {'edge': edge.tolist(), 'bits': bits.astype(int).tolist()}, 'stream': e.flush().hex()})
     return out
+
+
+def make_rans_random():
+    """random streams of the reference's BinaryRansCoder and IndexedRansCoder (the cases of tests/test_rans_golden.py
+    test_against_live_reference): inputs and the reference's outputs"""
+    import rans_ext_cpp as R
+    rng = np.random.default_rng(99)
+    cases = []
+    for _ in range(10):
+        n = int(rng.integers(1, 3000))
+        prob = np.clip(np.round(rng.beta(.3, .3, (1, n)) * 65536), 1, 65535).astype(np.uint32)
+        bits = rng.random((1, n)) < prob / 65536
+        binary = R.BinaryRansCoder(1).encode(bits, prob)[0]
+        hist = rng.integers(0, 50, int(rng.integers(2, 41))).astype(np.float64)
+        hist[0] += 1
+        sym = rng.choice(len(hist), size=(1, n), p=hist / hist.sum()).astype(np.int32) - 7
+        c = R.IndexedRansCoder(False, 1)
+        c.init_with_pmfs(hist[None].copy(), np.array([-7], np.int32))
+        cases.append({'prob': prob[0].tolist(), 'bits': ''.join('1' if b else '0' for b in bits[0]), 'binary': binary.hex(),
+                      'hist': hist.tolist(), 'offset': -7, 'symbols': sym[0].tolist(), 'cdfs': c.get_cdfs(),
+                      'indexed': c.encode(sym)[0].hex()})
+    return {'cases': cases}
 
 
 def make_morton():
@@ -1863,7 +1886,7 @@ def make_codec_color_chain():
 
 
 def main():
-    for name, fn in (('get_keep', make_get_keep), ('codec_lossl', make_codec_lossl), ('codec_color', make_codec_color), ('codec_v2', make_codec_v2), ('codec_v2_chain', make_codec_v2_chain), ('codec_v2_partitions_chain', make_codec_v2_partitions_chain), ('codec_color_chain', make_codec_color_chain), ('codec_color_partitions_chain', make_codec_color_partitions_chain), ('codec_int', make_codec_int), ('codec_v3', make_codec_v3), ('hilbert', make_hilbert), ('me_semantics', make_me_semantics), ('entropy_model_hyperprior', make_entropy_model_hyperprior), ('entropy_model_indexed', make_entropy_model_indexed), ('ptq_import', make_ptq_import), ('kdtree', make_kdtree), ('entropy_model', make_entropy_model), ('rans', make_rans), ('morton', make_morton), ('byteslist', make_byteslist), ('explut', make_explut)):
+    for name, fn in (('get_keep', make_get_keep), ('codec_lossl', make_codec_lossl), ('codec_color', make_codec_color), ('codec_v2', make_codec_v2), ('codec_v2_chain', make_codec_v2_chain), ('codec_v2_partitions_chain', make_codec_v2_partitions_chain), ('codec_color_chain', make_codec_color_chain), ('codec_color_partitions_chain', make_codec_color_partitions_chain), ('codec_int', make_codec_int), ('codec_v3', make_codec_v3), ('hilbert', make_hilbert), ('me_semantics', make_me_semantics), ('entropy_model_hyperprior', make_entropy_model_hyperprior), ('entropy_model_indexed', make_entropy_model_indexed), ('ptq_import', make_ptq_import), ('kdtree', make_kdtree), ('entropy_model', make_entropy_model), ('rans', make_rans), ('rans_random', make_rans_random), ('morton', make_morton), ('byteslist', make_byteslist), ('explut', make_explut)):
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
         data = fn()

@@ -22,7 +22,7 @@ def test_two_ranks_on_one_device_report_replicas_and_the_ddp_step():
     env = dict(os.environ, FPCC_BENCH_ONE_DEVICE='1', FPCC_BENCH_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--ddp-steps', '3',
-           '--resolution', '512']
+           '--resolution', '512', '--full']
     proc = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-3000:]
     lines = [l for l in proc.stdout.splitlines() if l.startswith('{')]

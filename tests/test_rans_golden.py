@@ -170,28 +170,27 @@ def test_batch_units_are_independent():
         assert (got == bits).all()
 
 
-def test_against_live_reference():
-    """When the reference's own coders were built here (oracle/_ref), compare random streams three ways."""
+def test_against_live_reference(golden_dir):
+    """Random streams of the reference's own coders (tests/golden/rans_random.json, written by them) against the oracle and the
+    product; when the reference's coders were built here (oracle/_ref) they are run live as well, three ways."""
+    with open(os.path.join(golden_dir, 'rans_random.json')) as f:
+        cases = json.load(f)['cases']
     R = _ref_modules()
-    if R is None:
-        pytest.skip('oracle/_ref not built (needs /root/reference)')
-    rng = np.random.default_rng(99)
-    for _ in range(10):
-        n = int(rng.integers(1, 3000))
-        prob = np.clip(np.round(rng.beta(.3, .3, (1, n)) * 65536), 1, 65535).astype(np.uint32)
-        bits = rng.random((1, n)) < prob / 65536
-        want = R.BinaryRansCoder(1).encode(bits, prob)[0]
-        assert orc.BinaryRansCoder(1).encode(bits, prob)[0] == want
-        assert prod.BinaryRansCoder(1).encode(bits, prob)[0] == want
-        hist = rng.integers(0, 50, int(rng.integers(2, 41))).astype(np.float64)
-        hist[0] += 1
-        sym = rng.choice(len(hist), size=(1, n), p=hist / hist.sum()).astype(np.int32) - 7
-        streams = []
-        for M in (R, orc, prod):
+    impls = ([R] if R is not None else []) + [orc, prod]
+    assert len(cases) == 10
+    for case in cases:
+        prob = np.array(case['prob'], np.uint32)[None]
+        bits = (np.frombuffer(case['bits'].encode(), np.uint8) == ord('1'))[None]
+        want = bytes.fromhex(case['binary'])
+        for M in impls:
+            assert M.BinaryRansCoder(1).encode(bits, prob)[0] == want
+        hist = np.array(case['hist'], np.float64)
+        sym = np.array(case['symbols'], np.int32)[None]
+        want = (case['cdfs'], bytes.fromhex(case['indexed']))
+        for M in impls:
             c = M.IndexedRansCoder(False, 1)
-            c.init_with_pmfs(hist[None].copy(), np.array([-7], np.int32))
-            streams.append((c.get_cdfs(), c.encode(sym)[0]))
-        assert streams[0] == streams[1] == streams[2]
+            c.init_with_pmfs(hist[None].copy(), np.array([case['offset']], np.int32))
+            assert (c.get_cdfs(), c.encode(sym)[0]) == want
 
 
 def test_multi_stream_encoder_matches_single():

@@ -2,7 +2,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r02pw; mkdir -p $O
 for v in 0 32768 12288; do
-  FPCC_POINTWISE_MIN_ROWS=$v timeout 200 python bench.py --steps 6 --warmup 2 --cpu-baseline 0 --secondary 0 --dump-trace $O/trace_$v.txt > $O/bench4_$v.json 2> $O/bench4_$v.err
+  FPCC_POINTWISE_MIN_ROWS=$v timeout 200 python bench.py --full --steps 6 --warmup 2 --cpu-baseline 0 --secondary 0 --dump-trace $O/trace_$v.txt > $O/bench4_$v.json 2> $O/bench4_$v.err
   python - <<PY
 rows=[l.split() for l in open("$O/trace_$v.txt")][1:]
 import collections

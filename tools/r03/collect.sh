@@ -2,7 +2,7 @@
 # gpurun_out/r03z (made by tools/r03/final.sh on the GPU box) -> profiles/r03/final_*   (run in the build container)
 S=gpurun_out/r03z; D=profiles/r03
 cp $S/stats/s_kernel_stats.csv $D/final_kernel_stats.csv
-{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0   (round 3, final state; 5 steps: warm-up, 3 timed, 1 clock-probe step)"; python profiles/summarize.py $S/stats/s_kernel_stats.csv 5; } > $D/final_summary.md
+{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0   (round 3, final state; 5 steps: warm-up, 3 timed, 1 clock-probe step)"; python profiles/summarize.py $S/stats/s_kernel_stats.csv 5; } > $D/final_summary.md
 python profiles/pmc_summary.py $S/fetch/p_counter_collection.csv $S/write/p_counter_collection.csv $D/final_pmc_traffic.json > $D/final_pmc_traffic.md
 python profiles/hbm_bandwidth.py $S/fetch $S/write > $D/final_hbm_bandwidth.md
 cp $S/conv_launches.txt $D/final_conv_launches.txt

@@ -9,6 +9,6 @@ for lvl in 1 2 3; do
     done
   done
 done
-timeout 300 python bench.py --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench.json
-FPCC_GROUPED_FOLD_ROWS=0 timeout 300 python bench.py --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench_nofold.json
-FPCC_GROUPED_FOLD_ROWS=50000 timeout 300 python bench.py --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench_fold50k.json
+timeout 300 python bench.py --full --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench.json
+FPCC_GROUPED_FOLD_ROWS=0 timeout 300 python bench.py --full --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench_nofold.json
+FPCC_GROUPED_FOLD_ROWS=50000 timeout 300 python bench.py --full --secondary 0 --cpu-baseline 0 2>&1 | tail -1 | tee $O/bench_fold50k.json

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 TAG=${1:-a}; WHAT=${2:-all}
 O=gpurun_out/r03p_$TAG; mkdir -p $O
-CMD="python3 bench.py --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0"
+CMD="python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0"
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/stats -o s --output-format csv -- $CMD > $O/stats.log 2>&1
 if [ "$WHAT" = "all" ]; then
 timeout 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch -o p --output-format csv -- $CMD > $O/fetch.log 2>&1

@@ -3,7 +3,7 @@
 S=gpurun_out/r04F; D=profiles/r04
 f() { find $S/$1 -name "$2" | head -1; }
 cp $(f stats s_kernel_stats.csv) $D/final_kernel_stats.csv
-{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0   (round 4, final state; 10 frames: 1 serial + 2 pipelined warm-up, 3 timed, 3 latency frames, 1 clock-probe frame)"; python profiles/summarize.py $D/final_kernel_stats.csv 10; } > $D/final_summary.md
+{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --cpu-baseline 0 --secondary 0   (round 4, final state; 10 frames: 1 serial + 2 pipelined warm-up, 3 timed, 3 latency frames, 1 clock-probe frame)"; python profiles/summarize.py $D/final_kernel_stats.csv 10; } > $D/final_summary.md
 python profiles/pmc_summary.py $(f fetch p_counter_collection.csv) $(f write p_counter_collection.csv) $D/final_pmc_traffic.json > $D/final_pmc_traffic.md
 python profiles/hbm_bandwidth.py $(dirname $(f fetch p_counter_collection.csv)) $(dirname $(f write p_counter_collection.csv)) > $D/final_hbm_bandwidth.md
 { echo; echo "## The helper kernels by launch size (profiles/hbm_bandwidth_by_size.py)"; echo; python profiles/hbm_bandwidth_by_size.py $(dirname $(f fetch p_counter_collection.csv)) $(dirname $(f write p_counter_collection.csv)); } >> $D/final_hbm_bandwidth.md

@@ -10,8 +10,8 @@ print('$2', d['value'], d['ms_per_step'], 'frac', r['frac'], 'kernel_ms', r['ker
 PY
 grep "step completions" ${1%.json}.err
 }
-timeout 600 python3 bench.py --cpu-baseline 1 --secondary 0 > $O/a.json 2> $O/a.err; show $O/a.json "baseline only"
-timeout 600 python3 bench.py --cpu-baseline 0 --secondary 1 > $O/b.json 2> $O/b.err; show $O/b.json "secondary only"
-timeout 600 python3 bench.py --cpu-baseline 0 --secondary 0 > $O/c.json 2> $O/c.err; show $O/c.json "neither"
-timeout 600 python3 bench.py > $O/d.json 2> $O/d.err; show $O/d.json "both"
-timeout 600 python3 bench.py --cpu-baseline 0 --secondary 0 > $O/e.json 2> $O/e.err; show $O/e.json "neither"
+timeout 600 python3 bench.py --full --cpu-baseline 1 --secondary 0 > $O/a.json 2> $O/a.err; show $O/a.json "baseline only"
+timeout 600 python3 bench.py --full --cpu-baseline 0 --secondary 1 > $O/b.json 2> $O/b.err; show $O/b.json "secondary only"
+timeout 600 python3 bench.py --full --cpu-baseline 0 --secondary 0 > $O/c.json 2> $O/c.err; show $O/c.json "neither"
+timeout 600 python3 bench.py --full > $O/d.json 2> $O/d.err; show $O/d.json "both"
+timeout 600 python3 bench.py --full --cpu-baseline 0 --secondary 0 > $O/e.json 2> $O/e.err; show $O/e.json "neither"

@@ -11,8 +11,8 @@ PY
 grep "step completions" ${1%.json}.err
 }
 for i in 1 2 3; do
-timeout 600 python3 bench.py --cpu-baseline 0 --secondary 0 > $O/c$i.json 2> $O/c$i.err; show $O/c$i.json "neither"
+timeout 600 python3 bench.py --full --cpu-baseline 0 --secondary 0 > $O/c$i.json 2> $O/c$i.err; show $O/c$i.json "neither"
 done
-timeout 600 python3 bench.py > $O/d.json 2> $O/d.err; show $O/d.json "default"
-timeout 600 python3 bench.py --steps 20 --warmup 5 > $O/d2.json 2> $O/d2.err; show $O/d2.json "default 20 5"
-timeout 600 python3 bench.py --steps 20 --warmup 5 --cpu-baseline 0 --secondary 0 > $O/d3.json 2> $O/d3.err; show $O/d3.json "neither 20 5"
+timeout 600 python3 bench.py --full > $O/d.json 2> $O/d.err; show $O/d.json "default"
+timeout 600 python3 bench.py --full --steps 20 --warmup 5 > $O/d2.json 2> $O/d2.err; show $O/d2.json "default 20 5"
+timeout 600 python3 bench.py --full --steps 20 --warmup 5 --cpu-baseline 0 --secondary 0 > $O/d3.json 2> $O/d3.err; show $O/d3.json "neither 20 5"

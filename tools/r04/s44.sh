@@ -14,5 +14,5 @@ print('$2', d['value'], d['ms_per_step'], 'frac', r['frac'], 'kernel_ms', r['ker
 PY
 }
 for w in 17 20 17 20; do
-  FPCC_ROW_WINDOW_LOG2=$w timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/w$w.json 2> $O/w$w.err; show $O/w$w.json "window 2^$w"
+  FPCC_ROW_WINDOW_LOG2=$w timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/w$w.json 2> $O/w$w.err; show $O/w$w.json "window 2^$w"
 done

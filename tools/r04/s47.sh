@@ -9,5 +9,5 @@ print('$2', d['value'], d['ms_per_step'], 'frac', r['frac'], 'kernel_ms', r['ker
 PY
 }
 for sw in 2e-4 5e-5 1e-3 2e-5 2e-4 5e-5; do
-  FPCC_SWITCH_INTERVAL=$sw timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/sw.json 2> $O/sw.err; show $O/sw.json "switch interval $sw"
+  FPCC_SWITCH_INTERVAL=$sw timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/sw.json 2> $O/sw.err; show $O/sw.json "switch interval $sw"
 done

@@ -10,6 +10,6 @@ PY
 }
 for res in 512 1024 2048; do
   for d in 2 1; do
-    timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 --steps 10 --warmup 3 --resolution $res --frames-in-flight $d > $O/fs.json 2> $O/fs.err; show $O/fs.json "res $res depth $d"
+    timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 --steps 10 --warmup 3 --resolution $res --frames-in-flight $d > $O/fs.json 2> $O/fs.err; show $O/fs.json "res $res depth $d"
   done
 done

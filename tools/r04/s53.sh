@@ -3,8 +3,8 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r04I; mkdir -p $O
 for i in 1 2 3 4 5 6; do
-  timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/z.json 2>/dev/null; python3 -c "
+  timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 > $O/z.json 2>/dev/null; python3 -c "
 import json; d=json.loads(open('$O/z.json').read().strip().splitlines()[-1]); print('20/5', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['kernel_ms_per_step'])"
-  timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 > $O/z.json 2>/dev/null; python3 -c "
+  timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 > $O/z.json 2>/dev/null; python3 -c "
 import json; d=json.loads(open('$O/z.json').read().strip().splitlines()[-1]); print('10/3', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['kernel_ms_per_step'])"
 done

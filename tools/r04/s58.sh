@@ -8,7 +8,7 @@ FPCC_OCCUPANCY_STREAM=1 timeout 300 python3 tools/r04/stress3.py 100 1024 2>&1 |
 for rep in 1 2 3; do
 for f in 0 1; do
   for d in 2 1; do
-  FPCC_OCCUPANCY_STREAM=$f timeout 300 python3 bench.py --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 --frames-in-flight $d > $O/q.json 2> $O/q.err
+  FPCC_OCCUPANCY_STREAM=$f timeout 300 python3 bench.py --full --cpu-baseline 0 --secondary 0 --steps 20 --warmup 5 --frames-in-flight $d > $O/q.json 2> $O/q.err
   python3 - <<PY
 import json
 d=json.loads(open('$O/q.json').read().strip().splitlines()[-1]); print('occupancy_stream=$f depth $d', d['value'], d['ms_per_step'], d['roofline']['kernel_ms_per_step'], d['config']['encode_ms'], d['config']['decode_ms'])

@@ -3,7 +3,7 @@
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r05; mkdir -p $O
 for b in ${BATCHES:-8 12 16}; do
-  timeout 900 python3 bench.py --batch $b --cpu-baseline 0 --secondary 0 > $O/g34_b$b.json 2> $O/g34_b$b.err
+  timeout 900 python3 bench.py --full --batch $b --cpu-baseline 0 --secondary 0 > $O/g34_b$b.json 2> $O/g34_b$b.err
   python3 - $O/g34_b$b.json $b <<'PY'
 import json, sys
 try:

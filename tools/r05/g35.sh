@@ -2,9 +2,9 @@
 # one frame at a time (the BASELINE definition of the metric): where the GPU idles
 cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r05/g35; rm -rf $O; mkdir -p $O
-timeout 600 rocprofv3 --kernel-trace --memory-copy-trace -d $O/gap -o p --output-format csv -- python3 bench.py --batch 1 --frames-in-flight 1 --steps 16 --warmup 2 --latency-frames 1 --cpu-baseline 0 --secondary 0 > $O/gap.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --memory-copy-trace -d $O/gap -o p --output-format csv -- python3 bench.py --full --batch 1 --frames-in-flight 1 --steps 16 --warmup 2 --latency-frames 1 --cpu-baseline 0 --secondary 0 > $O/gap.log 2>&1
 tail -2 $O/gap.log | cut -c1-400
-python3 profiles/step_gaps.py $(find $O/gap -name p_kernel_trace.csv | head -1) "one frame at a time (bench.py --batch 1 --frames-in-flight 1 --steps 16 --warmup 2 --latency-frames 1)" > $O/step_gaps_one_frame.md 2>&1
+python3 profiles/step_gaps.py $(find $O/gap -name p_kernel_trace.csv | head -1) "one frame at a time (bench.py --full --batch 1 --frames-in-flight 1 --steps 16 --warmup 2 --latency-frames 1)" > $O/step_gaps_one_frame.md 2>&1
 cat $O/step_gaps_one_frame.md
 python3 - $(find $O/gap -name p_kernel_trace.csv | head -1) $(find $O/gap -name p_memory_copy_trace.csv | head -1) $O <<'PY'
 import csv, sys, os

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 O=gpurun_out/r05; mkdir -p $O
 run() { # name, env assignments...
   local name=$1; shift
-  env "$@" timeout 600 python3 bench.py --cpu-baseline 0 --secondary 0 --latency-frames 2 --steps 8 > $O/g41_$name.json 2> $O/g41_$name.err
+  env "$@" timeout 600 python3 bench.py --full --cpu-baseline 0 --secondary 0 --latency-frames 2 --steps 8 > $O/g41_$name.json 2> $O/g41_$name.err
   python3 - $O/g41_$name.json "$name" <<'PY'
 import json, sys
 try:

@@ -4,13 +4,13 @@ S=gpurun_out/r06F; D=profiles/r06
 f() { find $S/$1 -name "$2" | head -1; }
 cp $(f stats s_kernel_stats.csv) $D/final_kernel_stats.csv
 FRAMES=${1:-116}
-{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 3 --warmup 1 --latency-frames 2 --cpu-baseline 0 --secondary 0   (round 6, final state; batch 16, two batches in flight: 16 reference frames + 4 one-frame-at-a-time frames + 2 warm-up and 3 timed batches of 16 + 1 clock-probe batch of 16 = $FRAMES frame-equivalents)"; python profiles/summarize.py $D/final_kernel_stats.csv $FRAMES; } > $D/final_summary.md
+{ echo "# rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --latency-frames 2 --cpu-baseline 0 --secondary 0   (round 6, final state; batch 16, two batches in flight: 16 reference frames + 4 one-frame-at-a-time frames + 2 warm-up and 3 timed batches of 16 + 1 clock-probe batch of 16 = $FRAMES frame-equivalents)"; python profiles/summarize.py $D/final_kernel_stats.csv $FRAMES; } > $D/final_summary.md
 cp $S/pmc_traffic.json $D/final_pmc_traffic.json; cp $S/pmc_traffic.md $D/final_pmc_traffic.md       # summarised on the GPU box (final.sh)
 python - <<PY
 import json
 p = '$D/final_pmc_traffic.json'
 d = json.load(open(p))
-d['_meta'] = {'frame_equivalents': $FRAMES, 'command': 'bench.py --steps 3 --warmup 1 --latency-frames 2 --cpu-baseline 0 --secondary 0 (batch 16, two batches in flight)'}
+d['_meta'] = {'frame_equivalents': $FRAMES, 'command': 'bench.py --full --steps 3 --warmup 1 --latency-frames 2 --cpu-baseline 0 --secondary 0 (batch 16, two batches in flight)'}
 json.dump(d, open(p, 'w'), indent=1)
 PY
 cp $S/hbm_bandwidth.md $D/final_hbm_bandwidth.md
