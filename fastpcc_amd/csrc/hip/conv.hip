@@ -115,9 +115,7 @@ __device__ __forceinline__ void stage_compute(const f32x4 (&ra)[C::G8], const fl
     }
 }
 
-// DBG (timing experiments only, results are wrong): bit 0 = every gathered row is row 0, bit 1 = every stage reads the weights of
-// chunk 0, bit 2 = no per-stage barrier (races on the W buffers)
-template <int NBT, int CH, int WM, int WN, int DBG = 0>
+template <int NBT, int CH, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN, 3) void k_conv_mfma(ConvArgs a) {
     using C = MfmaCfg<NBT, CH, WM, WN>;
     constexpr int C_OUT = C::C_OUT;
@@ -128,8 +126,6 @@ __global__ __launch_bounds__(64 * WM * WN, 3) void k_conv_mfma(ConvArgs a) {
     __shared__ int32_t s_nbr[kMaxOffsets * TM];
     __shared__ int32_t s_row[TM];          // output row of each tile position (-1 past the end)
     __shared__ unsigned s_mask[WM];
-    __shared__ int32_t s_zero_idx[32];     // DBG bit 0: thirty-two times row 0
-    if (DBG & 1) { if (threadIdx.x < 32) s_zero_idx[threadIdx.x] = 0; }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -203,11 +199,11 @@ __global__ __launch_bounds__(64 * WM * WN, 3) void k_conv_mfma(ConvArgs a) {
             }
 #pragma unroll
             for (int g8 = 0; g8 < C::G8; ++g8) ra_cur[g8] = ra_nxt[g8];
-            fetch_a<C, CH>(a, (DBG & 1) ? s_zero_idx : my_nbr + k_next * TM, cc_next, li, lh, ra_nxt);
-            fetch_w<C, CH>(wg, c_in, tid, (DBG & 2) ? 0 : k_next, (DBG & 2) ? 0 : cc_next, rw);
+            fetch_a<C, CH>(a, my_nbr + k_next * TM, cc_next, li, lh, ra_nxt);
+            fetch_w<C, CH>(wg, c_in, tid, k_next, cc_next, rw);
             if ((wmask >> k_cur) & 1u) stage_compute<C, CH>(ra_cur, sW + (s & 1) * CH * C_OUT, wc, li, lh, acc);
             stash_w<C>(sW + ((s + 1) & 1) * CH * C_OUT, tid, rw);
-            if (!(DBG & 4)) __syncthreads();
+            __syncthreads();
             k_cur = k_next;
         }
     }
@@ -337,15 +333,13 @@ struct WaveCfg {
 // consumed ra[g8] / rb[g8][*] the same registers are loaded with group g8 of the NEXT stage, so every load has a whole stage
 // of MFMAs to land and nothing is copied.  (A ring of 2-4 whole-stage buffers, refilled after the stage's last MFMA, was
 // 30-50 % slower on every map size: profiles/r02/wave_kernel_sweeps.md.)
-// DBG (timing experiments only, results are wrong): bit 0 = every gathered row is row 0 (no gather traffic), bit 1 = every
-// stage reads the weights of chunk 0 (B stream stays in the vector L1)
 // OG = 4 ("grouped" evaluation, summation order 3): the four waves of a workgroup share ONE unit and split its kernel offsets into
 // the four fixed contiguous groups of offset_group_begin(); each wave runs the order-1 chain of its group from zero, the partial
 // sums meet in LDS and are added as ((g0 + g1) + g2) + g3, then bias / activation.  A unit's serial chain of (offset, chunk)
 // stages is four times shorter and the launch has four times the waves: what maps of a few thousand to a few ten thousand rows
 // lack (one partial round of waves, each latency-bound on its own chain).  The groups are a function of the offset index alone,
 // so a row's result does not depend on which rows share its block.
-// DBG bit 4 (value 16): s_memtime stamps of one wave's life -- kernel entry, neighbour table read, first operands requested, the top
+// STAMPS (knob 3 = 16; results exact): s_memtime stamps of one wave's life -- kernel entry, neighbour table read, first operands requested, the top
 // of every (offset, chunk) stage, loop end, partial sums exchanged, outputs stored -- for profiles/r04/small_level_stage.md.  A stamp
 // is one LDS store by lane 0 with the exec mask narrowed in place (no branch: a branch in the stage loop makes hipcc drain vmcnt);
 // every wave copies its kStampSlots stamps to the buffer set with fpcc_conv_debug_stamps() when it ends.
@@ -355,32 +349,27 @@ struct WaveCfg {
 // t = p0, t = t + p1, t = t + p2, t = t + p3 with p_g = 0 for a group without a present offset -- bit for bit what the four waves of
 // OG == 4 leave behind, without their LDS exchange, barrier and wait for the slowest group.  For maps with many row blocks, where
 // the fourfold parallelism of OG == 4 buys nothing (272 K rows: 100 against 95 TFLOP/s, profiles/r03/grouped_fold.md).
-// ASTAGE (experiment, same bits): the A fragments of the NEXT stage are requested all at once at the top of a stage into a second
-// register set (the four 32-byte pieces of a gathered 128-byte line are then touched back to back instead of a quarter stage apart).
 // PERSIST (round 4; needs a row-major table, conv_common.h): a wave (OG == 1) / workgroup (OG == 4) walks units first, first + stride, ...
 // of the launch order instead of one, and requests the NEXT unit's table rows and output rows while it computes the current one: on a
 // loaded chip the prologue's dependent loads (row order -> table rows -> gather addresses) took a wave 20-70 K cycles and its stores
 // 20-40 K, a fifth of its life in which it feeds no MFMA (profiles/r04/prologue_epilogue.md).  Same chains, same bits.
-// WPW (OG == 1 only): waves per workgroup.  The waves of a workgroup share nothing but the launch, and a workgroup's slot on the CU is
-// held until its SLOWEST wave has finished: with one wave per workgroup a finished wave's slot is refilled at once.
-template <int NBW, int CH, int SB, int DBG = 0, int OG = 1, bool FOLD = false, bool ASTAGE = false, bool PERSIST = false, int WPW = 4>
-__global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>::MIN_WAVES)) void k_conv_wave(ConvArgs a, const float *__restrict__ wp,
+template <int NBW, int CH, int SB, bool STAMPS = false, int OG = 1, bool FOLD = false, bool PERSIST = false>
+__global__ __launch_bounds__(256, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>::MIN_WAVES)) void k_conv_wave(ConvArgs a, const float *__restrict__ wp,
                                                                                                            int nbt, unsigned n_units,
                                                                                                            unsigned *unit_counter = nullptr) {
     constexpr int G8 = CH / 8;
-    static_assert(OG == 1 || WPW == 4, "the four waves of a grouped workgroup are its four offset groups");
-    __shared__ int32_t s_nbr_all[WPW][32 * 32];    // [offset (padded to 32)][row] per wave
+    __shared__ int32_t s_nbr_all[4][32 * 32];    // [offset (padded to 32)][row] per wave
     __shared__ float s_part[OG == 4 ? 4 * 16 * NBW * 64 : 1];
-    __shared__ unsigned long long s_stamp[(DBG & 16) ? 4 * kStampSlots : 1];
+    __shared__ unsigned long long s_stamp[STAMPS ? 4 * kStampSlots : 1];
     __shared__ unsigned s_next[(PERSIST && OG == 4) ? 4 : 1];   // OG == 4: {unit, pass tag} x 2, written by wave 0 for its workgroup
-#define FPCC_STAMP(i) do { if (DBG & 16) stamp_lds(&s_stamp[wv * kStampSlots + (i)]); } while (0)
+#define FPCC_STAMP(i) do { if (STAMPS) stamp_lds(&s_stamp[wv * kStampSlots + (i)]); } while (0)
 
     // the wave index is wave-uniform, but hipcc only knows that when told: everything derived from it (the wave's offset group, its
     // offset mask, the stage iterator) otherwise lives in VGPRs, and the loop control below becomes ~25 vector instructions and
     // three exec-mask branches per stage instead of scalar code beside the MFMAs
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int li = lane & 31, lh = lane >> 5;
-    if (DBG & 16) {
+    if (STAMPS) {
         for (int i = lane; i < kStampSlots; i += 64) s_stamp[wv * kStampSlots + i] = 0;
         __builtin_amdgcn_wave_barrier();
     }
@@ -389,8 +378,7 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
     // unit = (32-row block, column group); the column groups of one row block are adjacent units (same workgroup: their A
     // rows hit the CU's vector L1).  Natural order: contiguous unit ranges per XCD; with a row order: dispatch order.
     const unsigned blk = (PERSIST || a.row_order) ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned slot = OG == 4 ? blk : blk * (unsigned)WPW + (unsigned)wv;
-    const unsigned n_slots = OG == 4 ? gridDim.x : gridDim.x * (unsigned)WPW;
+    const unsigned slot = OG == 4 ? blk : blk * 4u + (unsigned)wv;
     // PERSIST: the first unit of a slot is its own index; every further one is drawn from a counter (*unit_counter starts at the number
     // of slots) WHILE the current unit is computed -- the units come heaviest first (fpcc_conv_tile_keys) and take different times, so
     // a fixed stride or a serpentine would leave the slots up to 10 % apart at the end (measured: slower than one unit per workgroup)
@@ -537,14 +525,13 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
         int step;
         auto set_offset = [&](int k) {
             int32_t idx = s_nbr[k * 32 + li];
-            if (DBG & 1) idx = idx < 0 ? idx : 0;
             const int32_t neg = idx >> 31;                        // 0 or ~0; a select here comes back as a branch (if-conversion)
             const uint64_t m = (uint64_t)(int64_t)neg, z = reinterpret_cast<uint64_t>(zero) & m;
             const int64_t row = idx & ~neg;
             a1 = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x1b + row * ld1) & ~m) | z);
             a2 = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x2b + row * ld2) & ~m) | z);
             step = CH & ~neg;
-            bpk = (DBG & 2) ? wp_g : wp_g + (int64_t)k * n_chunks * chunk_floats;
+            bpk = wp_g + (int64_t)k * n_chunks * chunk_floats;
         };
         // fetch position: the next (offset, chunk) stage whose operands are to be requested; past the last stage it stays
         // on the last one (re-read, never used)
@@ -555,7 +542,7 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
         auto next_stage = [&]() {
             const bool in1 = cc_f < n1;                           // wave-uniform
             ap = (in1 ? a1 : a2) + (in1 ? cc_f : cc_f - n1) * step;
-            bp = (DBG & 2) ? bpk : bpk + cc_f * chunk_floats;
+            bp = bpk + cc_f * chunk_floats;
             if (cc_f + 1 < n_chunks) {
                 ++cc_f;
             } else {
@@ -571,18 +558,10 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
         // wait counts at the loop head are merged over both ways into it, and a different order here (the scheduler reverses
         // it if left alone) turns them into vmcnt(0) on every iteration.
         next_stage();
-        f32x4 ran[ASTAGE ? G8 : 1];
-        if (ASTAGE) {
-#pragma unroll
-            for (int g8 = 0; g8 < G8; ++g8) {
-                __builtin_amdgcn_sched_barrier(0);
-                ra[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
-            }
-        }
 #pragma unroll
         for (int g8 = 0; g8 < G8; ++g8) {
             __builtin_amdgcn_sched_barrier(0);
-            if (!ASTAGE) ra[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
+            ra[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
 #pragma unroll
             for (int nb = 0; nb < NBW; ++nb) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -607,13 +586,6 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
             }
             next_stage();                                       // stage s + 1
             __builtin_amdgcn_sched_barrier(SB);
-            if (ASTAGE) {
-#pragma unroll
-                for (int g8 = 0; g8 < G8; ++g8) {
-                    ran[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
-                    __builtin_amdgcn_sched_barrier(SB);
-                }
-            }
 #pragma unroll
             for (int g8 = 0; g8 < G8; ++g8) {
                 const f32x4 av = ra[g8];
@@ -627,17 +599,12 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
                 for (int nb = 0; nb < NBW; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, rb[g8][nb].w, acc[nb], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(SB);
                 // the registers of this group are free now: refill them for the next stage
-                if (!ASTAGE) ra[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
+                ra[g8] = *reinterpret_cast<const f32x4 *>(ap + 8 * g8);
 #pragma unroll
                 for (int nb = 0; nb < NBW; ++nb) {
                     __builtin_amdgcn_sched_barrier(SB);
                     rb[g8][nb] = *reinterpret_cast<const f32x4 *>(bp + ((int64_t)g8 * nbt + nb) * 256);
                 }
-                __builtin_amdgcn_sched_barrier(SB);
-            }
-            if (ASTAGE) {
-#pragma unroll
-                for (int g8 = 0; g8 < G8; ++g8) ra[g8] = ran[g8];
                 __builtin_amdgcn_sched_barrier(SB);
             }
         }
@@ -696,7 +663,7 @@ __global__ __launch_bounds__(64 * WPW, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>
                 a.out[dst * a.ldo + 32 * ((int)cg * NBW + nb) + li] = finish(v, bias4[nb], a.act, slope, a.clip);
             }
         }
-        if (DBG & 16) {
+        if (STAMPS) {
             FPCC_STAMP(42);
             if (lane == 0) {
                 s_stamp[wv * kStampSlots + 44] = (unsigned long long)n_stages;
@@ -931,30 +898,25 @@ int launch_mfma_cfg(ConvArgs a, hipStream_t s) {
     constexpr int TM = 32 * WM;
     const unsigned tiles = (unsigned)((a.n_out + TM - 1) / TM);
     const dim3 grid(tiles, a.groups), block(64 * WM * WN);
-    const int dbg = (NBT == 4 && CH == 32) ? knob(3) : 0;          // kKnobWaveDbg: experiments on the 128-column shapes only
-    if (dbg == 1) hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN, 1>), grid, block, 0, s, a);
-    else if (dbg == 2) hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN, 2>), grid, block, 0, s, a);
-    else if (dbg == 3) hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN, 3>), grid, block, 0, s, a);
-    else if (dbg == 4) hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN, 4>), grid, block, 0, s, a);
-    else if (dbg == 7) hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN, 7>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN>), grid, block, 0, s, a);
+    hipLaunchKernelGGL((k_conv_mfma<NBT, CH, WM, WN>), grid, block, 0, s, a);
     return check_hip(hipGetLastError(), "k_conv_mfma");
 }
 
 // Tuning knobs (fpcc_conv_set_tuning; initial values from the environment).  None of them changes a result EXCEPT
 // kKnobGroupedOff (experiments only: 1 = multi-offset layers in order 1 on the plain wave kernel instead of grouped / order 3),
 // which is therefore refused unless the process runs with FPCC_EXPERIMENT=1 and has no environment variable.
-enum { kKnobWaveOn = 0, kKnobWaveNbw = 1, kKnobWaveSb = 2, kKnobWaveDbg = 3, kKnobGroupedFoldRows = 4, kKnobMfmaCfg = 5, kKnobPointwiseRows = 6,
+// kKnobStamps (0 | 16: the stamped builds of the grouped and the LDS-operand kernel, same bits) has no environment variable either.
+enum { kKnobWaveOn = 0, kKnobWaveNbw = 1, kKnobWaveSb = 2, kKnobStamps = 3, kKnobGroupedFoldRows = 4, kKnobMfmaCfg = 5, kKnobPointwiseRows = 6,
        kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobCount = 13 };
 int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 int knob(int k) {
     if (g_knob[k] < 0) {
-        static const char *names[kKnobCount] = {"FPCC_CONV_WAVE", "FPCC_WAVE_NBW", "FPCC_WAVE_SB", "FPCC_WAVE_DBG", "FPCC_GROUPED_FOLD_ROWS",
+        static const char *names[kKnobCount] = {"FPCC_CONV_WAVE", "FPCC_WAVE_NBW", "FPCC_WAVE_SB", "", "FPCC_GROUPED_FOLD_ROWS",
                                                 "FPCC_MFMA_TILE", "FPCC_POINTWISE_MIN_ROWS", "", "FPCC_GROUPED_NBW",
                                                 "FPCC_WAVE22_MIN_ROWS", "FPCC_LDS_MIN_ROWS", "FPCC_LDS_ROW_BLOCKS",
                                                 "FPCC_CONV_PERSIST"};
         static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0};
-        const char *e = k == kKnobGroupedOff ? nullptr : getenv(names[k]);
+        const char *e = names[k][0] ? getenv(names[k]) : nullptr;
         g_knob[k] = e ? atoi(e) : defaults[k];
     }
     return g_knob[k];
@@ -992,12 +954,8 @@ int launch_wave_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) 
     const int64_t units = row_blocks * (nbt / NBW);
     if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
     const dim3 grid((unsigned)((units + 3) / 4), a.groups);
-    const int dbg = knob(kKnobWaveDbg);
     // knob FPCC_WAVE_SB=1: the address arithmetic of the next stage may be scheduled between the MFMAs
-    if (dbg == 1) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 1>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (dbg == 2) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 2>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (dbg == 3) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 3>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (knob(kKnobWaveSb)) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    if (knob(kKnobWaveSb)) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     else hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     return check_hip(hipGetLastError(), "k_conv_wave");
 }
@@ -1063,26 +1021,20 @@ int launch_grouped_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t 
     const int64_t row_blocks = (a.n_out + 31) / 32;
     const int64_t units = row_blocks * (nbt / NBW);
     if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
-    const int dbg = knob(kKnobWaveDbg);
+    const bool stamps = knob(kKnobStamps) != 0;
     const int64_t slots = persist_slots();
-    if (dbg == 0 && persist_ok(a) && units > slots) {
+    if (!stamps && persist_ok(a) && units > slots) {
         int rc = FPCC_OK;
         unsigned *counter = next_unit_counter((unsigned)slots, s, &rc);
         if (rc != FPCC_OK) return rc;
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 0, 4, false, false, true>), dim3((unsigned)slots, 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units,
+        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 4, false, true>), dim3((unsigned)slots, 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units,
                            counter);
         return check_hip(hipGetLastError(), "k_conv_wave(grouped, persistent)");
     }
-    if (dbg == 16)                      // stage stamps (fpcc_conv_debug_stamps)
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 16, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (NBW == 1 && dbg == 17)     // + no gather traffic / weights from one chunk / both (results wrong)
-        hipLaunchKernelGGL((k_conv_wave<1, 32, 0x6, 17, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (NBW == 1 && dbg == 18)
-        hipLaunchKernelGGL((k_conv_wave<1, 32, 0x6, 18, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else if (NBW == 1 && dbg == 19)
-        hipLaunchKernelGGL((k_conv_wave<1, 32, 0x6, 19, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    if (stamps)                         // stage stamps (fpcc_conv_debug_stamps)
+        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, true, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     else
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 0, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 4>), dim3((unsigned)units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     return check_hip(hipGetLastError(), "k_conv_wave(grouped)");
 }
 
@@ -1092,25 +1044,16 @@ int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s
     const int64_t units = ((a.n_out + 31) / 32) * (nbt / NBW);
     if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
     const int64_t slots = persist_slots();
-    if (knob(kKnobWaveDbg) == 0 && persist_ok(a) && (units + 3) / 4 > slots) {
+    if (!knob(kKnobStamps) && persist_ok(a) && (units + 3) / 4 > slots) {
         int rc = FPCC_OK;
         unsigned *counter = next_unit_counter((unsigned)(4 * slots), s, &rc);
         if (rc != FPCC_OK) return rc;
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 0, 1, true, false, true>), dim3((unsigned)slots, 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units,
+        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, true, true>), dim3((unsigned)slots, 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units,
                            counter);
         return check_hip(hipGetLastError(), "k_conv_wave(folded, persistent)");
     }
-    if (knob(kKnobWaveDbg) == 64) {                  // experiment: one wave per workgroup
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 0, 1, true, false, false, 1>), dim3((unsigned)units, a.groups), dim3(64), 0, s, a, wp, nbt,
-                           (unsigned)units);
-        return check_hip(hipGetLastError(), "k_conv_wave(folded, one wave per workgroup)");
-    }
-    if (NBW == 2 && knob(kKnobWaveDbg) == 32)        // experiment: A fragments a whole stage at a time
-        hipLaunchKernelGGL((k_conv_wave<2, 32, 0x6, 0, 1, true, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a, wp, nbt,
-                           (unsigned)units);
-    else
-        hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, 0, 1, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a, wp, nbt,
-                           (unsigned)units);
+    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a, wp, nbt,
+                       (unsigned)units);
     return check_hip(hipGetLastError(), "k_conv_wave(folded)");
 }
 
@@ -1119,7 +1062,7 @@ int launch_grouped(const ConvArgs &a, const float *wp, hipStream_t s) {
     // both operands through LDS (conv_lds.hip) on maps of at least FPCC_LDS_MIN_ROWS rows (knob 10; 0 = never); same order 3
     const int64_t lds_rows = knob(kKnobLdsRows);
     if (lds_rows > 0 && a.n_out >= lds_rows) {
-        const int rc = launch_conv_lds(a, wp, knob(kKnobLdsRowBlocks), knob(kKnobWaveDbg) & 63, s);
+        const int rc = launch_conv_lds(a, wp, knob(kKnobLdsRowBlocks), knob(kKnobStamps) != 0, s);
         if (rc != -1) return rc;
     }
     const int64_t fold_rows = knob(kKnobGroupedFoldRows);
@@ -1168,7 +1111,7 @@ int launch_wave(const ConvArgs &a, const float *wp, hipStream_t s) {
 // layout, rows are contiguous in memory) and the outputs stored.  Two to three waves per SIMD overlap one wave's loads with
 // another's MFMAs.  Same FMA chain per output element as k_conv_wave / k_conv_mfma (chunks ascending, groups of 8 channels
 // ascending, 0,4,1,5,2,6,3,7 inside a group): summation order 1, results bit-identical.
-template <int NBW, int NCH, int DBG = 0>
+template <int NBW, int NCH>
 __global__ __launch_bounds__(256, 2) void k_pointwise_wave(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_row_blocks,
                                                            unsigned waves_per_cg) {
     constexpr int AC = NCH < 4 ? NCH : 4;          // chunks of A held at a time (16 VGPRs each)
@@ -1205,12 +1148,10 @@ __global__ __launch_bounds__(256, 2) void k_pointwise_wave(ConvArgs a, const flo
     auto row_ptrs = [&](unsigned rbk, const float *&q1, const float *&q2) {
         int64_t row = (int64_t)rbk * 32 + li;
         if (row >= a.n_out) row = a.n_out - 1;                  // tail block / past the end: re-read the last row, never stored
-        if (DBG & 1) row = lane & 1;                            // timing experiment: (almost) no A traffic
         q1 = a.x1 + row * a.ld1 + 4 * lh;
         q2 = a.x2 ? a.x2 + row * a.ld2 + 4 * lh : q1;
     };
     auto fetch = [&](const float *q1, const float *q2, int cc, int g8) -> f32x4 {
-        if (DBG & 8) { const float v = (float)(lane + g8 + cc); return f32x4{v, v + 1.0f, v + 2.0f, v + 3.0f}; }
         const float *src = cc < n1 ? q1 + 32 * cc : q2 + 32 * (cc - n1);             // wave-uniform
         return *reinterpret_cast<const f32x4 *>(src + 8 * g8);
     };
@@ -1277,7 +1218,7 @@ __global__ __launch_bounds__(256, 2) void k_pointwise_wave(ConvArgs a, const flo
             const int r = r0 + qr;
             const f32x4 v = *reinterpret_cast<const f32x4 *>(tile + r * TW + 4 * qc);
             const int64_t o = row0 + r;
-            if (o < a.n_out && !((DBG & 4) && v.x != 12345.678f))
+            if (o < a.n_out)
                 *reinterpret_cast<f32x4 *>(a.out + o * a.ldo + 32 * (int)cg * NBW + 4 * qc) = v;
         }
         __builtin_amdgcn_wave_barrier();
@@ -1294,12 +1235,7 @@ int launch_pointwise_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_
     unsigned waves_per_cg = (256u * 4u * 2u) / n_cg;            // two waves per SIMD on the whole chip
     if (waves_per_cg > row_blocks) waves_per_cg = row_blocks;
     const unsigned waves = waves_per_cg * n_cg;
-    const int dbg = (NBW == 2 && NCH == 4) ? knob(kKnobWaveDbg) : 0;       // experiments on the 128 -> 128 shape only
-    if (dbg == 1) hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH, 1>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
-    else if (dbg == 4) hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH, 4>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
-    else if (dbg == 5) hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH, 5>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
-    else if (dbg == 12) hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH, 12>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
-    else hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
+    hipLaunchKernelGGL((k_pointwise_wave<NBW, NCH>), dim3((waves + 3) / 4), dim3(256), 0, s, a, wp, nbt, row_blocks, waves_per_cg);
     return check_hip(hipGetLastError(), "k_pointwise_wave");
 }
 
@@ -1475,6 +1411,8 @@ extern "C" int fpcc_conv_set_tuning(int which, int value) {
         if (!e || atoi(e) != 1)
             return fail_arg("conv_set_tuning: the summation order is part of the stream format (FPCC_EXPERIMENT=1 to override)");
     }
+    if (which == kKnobStamps && value != 0 && value != 16)
+        return fail_arg("conv_set_tuning: knob 3 is 0 or 16 (stamped builds); the timing ablations are no longer part of the library");
     const int before = knob(which);
     g_knob[which] = value < 0 ? 0 : value;
     return before;

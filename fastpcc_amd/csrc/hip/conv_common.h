@@ -74,6 +74,6 @@ int set_lds_stamp_buffer(unsigned long long *buf, long long cap);   // conv_lds.
 
 // conv_lds.hip: order-3 (folded) evaluation of a multi-offset layer with both operands staged through LDS; `rows_log` selects the
 // tile (2, 3 or 4 row blocks of 32 in lockstep).  Returns FPCC_OK, an error, or -1 when the shape is not covered.
-int launch_conv_lds(const ConvArgs &a, const float *wp, int row_blocks, int dbg, hipStream_t s);
+int launch_conv_lds(const ConvArgs &a, const float *wp, int row_blocks, bool stamps, hipStream_t s);
 
 }  // namespace fpcc

@@ -36,29 +36,27 @@ struct LdsCfg {
     static constexpr int MIN_WAVES = WGS * WAVES / 4 > 4 ? 4 : WGS * WAVES / 4;          // per SIMD
 };
 
-// DBG (timing experiments only, results are wrong): bit 0 = every gathered row is row 0, bit 1 = every stage reads the weights of chunk 0,
-// bit 2 = no fragment reads (the MFMAs run on whatever the registers hold), bit 3 = no DMAs, bit 4 = no wait / barrier per stage;
-// bit 5 (results stay exact without the other bits) = stamps: [0] entry, [1] masks known, [2] first DMAs issued, [40] loop end, [41] folded,
+// STAMPS (results exact): [0] entry, [1] masks known, [2] first DMAs issued, [40] loop end, [41] folded,
 // [42] stored, [43] stages this wave computed, [44] stages of the workgroup, [45] workgroup << 8 | wave, [46] HW_ID, [47] XCC_ID
-template <int R, int NBW, int DBG>
+template <int R, int NBW, bool STAMPS>
 __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_lds(ConvArgs a, const float *__restrict__ wp, int nbt,
                                                                                unsigned n_tiles) {
     using C = LdsCfg<R, NBW>;
     constexpr int ROWS = C::ROWS;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS + ((DBG & 32) ? C::WAVES * kStampSlots * 8 : 0)];   // ONE array
+    __shared__ __attribute__((aligned(16))) unsigned char smem[C::LDS + (STAMPS ? C::WAVES * kStampSlots * 8 : 0)];   // ONE array
     unsigned *const s_mask = reinterpret_cast<unsigned *>(smem + 2 * C::BUF);
     unsigned long long *const s_stamp = reinterpret_cast<unsigned long long *>(smem + C::LDS);
-#define FPCC_STAMP(i) do { if (DBG & 32) stamp_lds(&s_stamp[wv * kStampSlots + (i)]); } while (0)
+#define FPCC_STAMP(i) do { if (STAMPS) stamp_lds(&s_stamp[wv * kStampSlots + (i)]); } while (0)
 
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = wv >> 1, c = wv & 1;                          // row block, column half of this wave
     const int li = lane & 31, lh = lane >> 5;
-    if (DBG & 32) {
+    if (STAMPS) {
         for (int i = lane; i < kStampSlots; i += 64) s_stamp[wv * kStampSlots + i] = 0;
         __builtin_amdgcn_wave_barrier();
     }
     FPCC_STAMP(0);
-    if (DBG & 32) stamp_lds_realtime(&s_stamp[wv * kStampSlots + 38]);
+    if (STAMPS) stamp_lds_realtime(&s_stamp[wv * kStampSlots + 38]);
     int n_computed = 0;
     const unsigned tile = a.row_order ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
     if (tile >= n_tiles) return;
@@ -167,7 +165,6 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 int32_t idx = idx_n[j];
-                if (DBG & 1) idx = idx < 0 ? idx : 0;
                 const bool ok = idx >= 0;
                 a1[j] = (ok ? a.x1 + (int64_t)idx * ld1 : zero) + ppiece[j];
                 a2[j] = (ok ? x2 + (int64_t)idx * ld2 : zero) + ppiece[j];
@@ -177,7 +174,6 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
         const int64_t chunk_floats = (int64_t)4 * nbt * 256;
         const float *const wp_l = wp + ((int64_t)c * NBW) * 256 + lane * 4;
         auto issue = [&](int k, int cc, int buf) {
-            if (DBG & 8) return;
             unsigned char *const base = smem + buf * C::BUF;
             const bool in1 = cc < n1;                                        // wave-uniform
 #pragma unroll
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
                 const float *src = in1 ? a1[j] + cc * step[j] : a2[j] + (cc - n1) * step[j];
                 __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + r * 4096 + (2 * c + j) * 1024), 16, 0, 0);
             }
-            const float *bsrc = wp_l + ((DBG & 2) ? 0 : ((int64_t)k * n_chunks + cc) * chunk_floats);
+            const float *bsrc = wp_l + ((int64_t)k * n_chunks + cc) * chunk_floats;
 #pragma unroll
             for (int t = 0; t < (4 * NBW + R - 1) / R; ++t) {
                 const int q = r + t * R;                                     // wave-uniform
@@ -213,10 +209,8 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
         FPCC_STAMP(2);
         for (int s = 0; s < n_stages; ++s) {
             // stage s has landed everywhere, and everyone is done with stage s - 1 (whose buffer the next DMAs overwrite)
-            if (!(DBG & 16)) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
-            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
             int k_n = k, cc_n = cc + 1;
             if (cc_n == n_chunks) {
                 cc_n = 0;
@@ -232,7 +226,7 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
                 issue(k_n, cc_n, (s + 1) & 1);
             }
             if ((wmask >> k) & 1u) {                                         // wave-uniform
-                if (DBG & 32) ++n_computed;
+                if (STAMPS) ++n_computed;
                 if (cc == 0) {
                     const int gk = offset_group_of(k, n_off);
                     if (gk != cur_g) {
@@ -245,16 +239,7 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
                 // fragments of group g8 + 1 are requested before the MFMAs of group g8 (two register sets): hipcc otherwise reads each
                 // group right before its use and exposes the LDS latency four times per stage
                 f32x4 av[2], bv[2][NBW];
-                if (DBG & 4) {
-#pragma unroll
-                    for (int sl = 0; sl < 2; ++sl) {
-                        av[sl] = f32x4{1.0f, 2.0f, 3.0f, 4.0f} * (float)lane;
-#pragma unroll
-                        for (int nb = 0; nb < NBW; ++nb) bv[sl][nb] = f32x4{0.5f, 0.25f, 0.125f, 1.0f} * (float)(nb + lane);
-                    }
-                }
                 auto read_group = [&](int g8, int slot) {
-                    if (DBG & 4) { asm volatile("" : "+v"(av[slot])); return; }
                     av[slot] = *reinterpret_cast<const f32x4 *>(base + a_frag + (((2 * g8 + lh) ^ a_swz) << 4));
 #pragma unroll
                     for (int nb = 0; nb < NBW; ++nb)
@@ -304,7 +289,7 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
         for (int nb = 0; nb < NBW; ++nb)
             a.out[o * a.ldo + 32 * (c * NBW + nb) + li] = finish(tsum[nb][q], bias[nb], a.act, slope, a.clip);
     }
-    if (DBG & 32) {
+    if (STAMPS) {
         FPCC_STAMP(42);
         stamp_lds_realtime(&s_stamp[wv * kStampSlots + 39]);
         if (lane == 0) {
@@ -323,17 +308,13 @@ __global__ __launch_bounds__(128 * R, (LdsCfg<R, NBW>::MIN_WAVES)) void k_conv_l
 }
 
 template <int R, int NBW>
-int launch_cfg(const ConvArgs &a, const float *wp, int nbt, int dbg, hipStream_t s) {
+int launch_cfg(const ConvArgs &a, const float *wp, int nbt, bool stamps, hipStream_t s) {
     constexpr int ROWS = 32 * R;
     const int64_t tiles = (a.n_out + ROWS - 1) / ROWS;
     if (tiles > 0x7fffffffll) return fail_arg("conv_f32: too many tiles");
     const dim3 grid((unsigned)tiles), block(128 * R);
-    switch (dbg) {
-#define FPCC_LDS_CASE(D) case D: hipLaunchKernelGGL((k_conv_lds<R, NBW, D>), grid, block, 0, s, a, wp, nbt, (unsigned)tiles); break;
-        FPCC_LDS_CASE(1) FPCC_LDS_CASE(2) FPCC_LDS_CASE(3) FPCC_LDS_CASE(4) FPCC_LDS_CASE(8) FPCC_LDS_CASE(16) FPCC_LDS_CASE(24) FPCC_LDS_CASE(28) FPCC_LDS_CASE(32) FPCC_LDS_CASE(60)
-#undef FPCC_LDS_CASE
-        default: hipLaunchKernelGGL((k_conv_lds<R, NBW, 0>), grid, block, 0, s, a, wp, nbt, (unsigned)tiles);
-    }
+    if (stamps) hipLaunchKernelGGL((k_conv_lds<R, NBW, true>), grid, block, 0, s, a, wp, nbt, (unsigned)tiles);
+    else hipLaunchKernelGGL((k_conv_lds<R, NBW, false>), grid, block, 0, s, a, wp, nbt, (unsigned)tiles);
     return check_hip(hipGetLastError(), "k_conv_lds");
 }
 
@@ -345,17 +326,17 @@ int set_lds_stamp_buffer(unsigned long long *buf, long long cap) {
     return FPCC_OK;
 }
 
-int launch_conv_lds(const ConvArgs &a, const float *wp, int row_blocks, int dbg, hipStream_t s) {
+int launch_conv_lds(const ConvArgs &a, const float *wp, int row_blocks, bool stamps, hipStream_t s) {
     const int nbt = a.c_out / 32;
     if ((nbt != 2 && nbt != 4) || a.groups != 1 || a.out_map || !a.nbr || a.n_off > kMaxOffsets || (a.c1 + a.c2) % 32 || a.c1 % 32) return -1;
     if (nbt == 4) {
-        if (row_blocks == 2) return launch_cfg<2, 2>(a, wp, nbt, dbg, s);
-        if (row_blocks == 3) return launch_cfg<3, 2>(a, wp, nbt, dbg, s);
-        if (row_blocks == 4) return launch_cfg<4, 2>(a, wp, nbt, dbg, s);
+        if (row_blocks == 2) return launch_cfg<2, 2>(a, wp, nbt, stamps, s);
+        if (row_blocks == 3) return launch_cfg<3, 2>(a, wp, nbt, stamps, s);
+        if (row_blocks == 4) return launch_cfg<4, 2>(a, wp, nbt, stamps, s);
     } else {
-        if (row_blocks == 2) return launch_cfg<2, 1>(a, wp, nbt, dbg, s);
-        if (row_blocks == 3) return launch_cfg<3, 1>(a, wp, nbt, dbg, s);
-        if (row_blocks == 4) return launch_cfg<4, 1>(a, wp, nbt, dbg, s);
+        if (row_blocks == 2) return launch_cfg<2, 1>(a, wp, nbt, stamps, s);
+        if (row_blocks == 3) return launch_cfg<3, 1>(a, wp, nbt, stamps, s);
+        if (row_blocks == 4) return launch_cfg<4, 1>(a, wp, nbt, stamps, s);
     }
     return -1;
 }

@@ -368,9 +368,7 @@ __device__ __forceinline__ int32_t epi_lean_elem(int32_t a, int32_t b, int32_t m
     return OUT_BITS == 8 ? min(max(r32, -128), 127) : r32;
 }
 
-// EDBG (timing experiments of the int8-output form, results wrong): 32 = the values are computed but not stored, 64 = stored without
-// being computed (the accumulator's low byte)
-template <int NB, int EDBG = 0>
+template <int NB>
 __device__ __forceinline__ void conv_i8_epilogue(const ConvI8Args &p, const i32x16 (&acc)[NB], const int32_t *my_rows, int col0, int lane) {
     const int li = lane & 31, lh = lane >> 5;
     const int64_t zp = p.zp ? p.zp[0] : 0;
@@ -415,21 +413,15 @@ __device__ __forceinline__ void conv_i8_epilogue(const ConvI8Args &p, const i32x
             // LDS first and writing whole 16-byte pieces of whole rows -- NB store instructions instead of 16 NB -- was built in round 5,
             // bit-exact, and not faster: 92.6 against 89.5 us on the 113 K-row level, profiles/r05/int8_stage.md.)
             int8_t *out = static_cast<int8_t *>(p.out) + col0 + li;
-            int32_t sink = 0;
 #define FPCC_I8_PUT(ELEM)                                                                                          \
             _Pragma("unroll") for (int reg = 0; reg < 16; ++reg) {                                                  \
                 int8_t *o = out + orow[reg] * p.ldo;                                                                \
-                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) {                                                 \
-                    if (EDBG & 64) o[32 * nb] = (int8_t)acc[nb][reg];                                               \
-                    else if (EDBG & 32) sink ^= (ELEM);                                                             \
-                    else o[32 * nb] = (int8_t)(ELEM);                                                               \
-                }                                                                                                   \
+                _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) o[32 * nb] = (int8_t)(ELEM);                      \
             }
             if (lean && hi) { FPCC_I8_PUT((epi_lean_elem<8, true>(acc[nb][reg], b[nb], m[nb], e))) }
             else if (lean) { FPCC_I8_PUT((epi_lean_elem<8, false>(acc[nb][reg], b[nb], m[nb], e))) }
             else { FPCC_I8_PUT((epi_fast_elem<8>(acc[nb][reg], b[nb], m[nb], e, bad_sign, bad_any))) }
 #undef FPCC_I8_PUT
-            if ((EDBG & 32) && sink == 0x12345678) out[0] = (int8_t)sink;
         } else if (!p.res) {
             int32_t *out = static_cast<int32_t *>(p.out) + col0 + li;
             if (lean && !hi) {
@@ -595,7 +587,7 @@ __global__ __launch_bounds__(256) void k_conv_i8(ConvI8Args p, int32_t *acc_out,
 // barrier per stage, 16-byte pieces XOR-swizzled so that the MFMA operand reads are conflict free), every wave gathers
 // its 32 A rows as full 128-byte lines into registers one stage ahead, and issues up to 4*NB MFMAs per stage.  Offsets
 // absent from the whole tile are skipped by the workgroup, offsets absent from a wave's rows by that wave.
-// Diagnostics (profiles/r05/int8_stage.md): s_memtime stamps of wave 0 of every workgroup of k_conv_i8_tiled<4, 16> in LDS slots, copied to
+// Diagnostics (profiles/r05/int8_stage.md): s_memtime stamps of wave 0 of every workgroup of k_conv_i8_tiled<4, true> in LDS slots, copied to
 // the buffer set with fpcc_conv_i8_debug_stamps when the workgroup ends.  A stamp is one LDS store by lane 0 with the exec mask narrowed
 // in place (no branch: a branch in the stage loop makes hipcc drain vmcnt).
 constexpr int kI8StampSlots = 48;
@@ -612,7 +604,7 @@ __device__ __forceinline__ void i8_stamp(unsigned long long *slot) {
 // chain of dependent round trips (row order -> kernel map -> operands) with nothing to hide them behind -- 41 % of its wave cycles are
 // parked at a wait (profiles/r05/int8_stage.md).  Half the columns is half the registers: four waves per SIMD, at the price of gathering
 // every A row once more.
-template <int NB, int DBG = 0, int MW = (NB == 4 ? 2 : 4)>   // DBG (timing experiments, results wrong): 1 no MFMA, 2 no gather (A from the zero row), 4 no W fetch
+template <int NB, bool STAMPS = false, int MW = (NB == 4 ? 2 : 4)>
 __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
     constexpr int COLS = 32 * NB;
     constexpr int W_PIECES = COLS * 8 / 256;                     // 16-byte pieces of one W tile per thread
@@ -620,12 +612,12 @@ __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
     extern __shared__ int32_t s_idx[];                           // [n_off][128] (dynamic: 13.5 KB for 27 offsets, 32 KB for 64)
     __shared__ int32_t s_row[128];
     __shared__ unsigned long long s_mask[4];
-    __shared__ unsigned long long s_i8_stamp[(DBG & 16) ? kI8StampSlots : 1];
-#define FPCC_I8_STAMP(i) do { if ((DBG & 16) && wave == 0) i8_stamp(&s_i8_stamp[(i)]); } while (0)
+    __shared__ unsigned long long s_i8_stamp[STAMPS ? kI8StampSlots : 1];
+#define FPCC_I8_STAMP(i) do { if (STAMPS && wave == 0) i8_stamp(&s_i8_stamp[(i)]); } while (0)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    if (DBG & 16) {
+    if (STAMPS) {
         if (tid < kI8StampSlots) s_i8_stamp[tid] = 0;
         __syncthreads();
     }
@@ -716,7 +708,7 @@ __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
 
     const int8_t *zero = g_zero_i8;
     auto fetch_a = [&](int k, int c, i32x4 (&ra)[4]) {
-        const int32_t idx = (DBG & 2) ? -1 : my_idx[k * 128];
+        const int32_t idx = my_idx[k * 128];
         const int8_t *arow = p.a + (int64_t)(idx >= 0 ? idx : 0) * p.lda;
 #pragma unroll
         for (int s4 = 0; s4 < 4; ++s4) {
@@ -729,7 +721,7 @@ __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
         for (int j = 0; j < W_PIECES; ++j) {
             const int piece = tid + 256 * j;
             const int col = col0 + (piece >> 3), koff = 128 * c + 16 * (piece & 7);
-            rw[j] = *reinterpret_cast<const i32x4 *>((col < p.c_out && koff < p.ldw && !(DBG & 4))
+            rw[j] = *reinterpret_cast<const i32x4 *>((col < p.c_out && koff < p.ldw)
                                                          ? p.w + ((int64_t)k * p.c_out + col) * p.ldw + koff : zero);
         }
     };
@@ -771,8 +763,6 @@ __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
                         const int part = 2 * s4 + lh;
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb)
-                            if (DBG & 1) acc[nb][0] += ra_cur[s4][0] + cB[part * COLS + ((32 * nb + li) ^ part)][0];
-                            else
                             acc[nb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(ra_cur[s4], cB[part * COLS + ((32 * nb + li) ^ part)],
                                                                            acc[nb], 0, 0, 0);
                     }
@@ -797,17 +787,8 @@ __global__ __launch_bounds__(256, MW) void k_conv_i8_tiled(ConvI8Args p) {
     }
 
     FPCC_I8_STAMP(38);                                           // last stage done
-    if (DBG & 8) {                                   // no epilogue
-        int32_t x = 0;
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) x ^= acc[nb][r];
-        if (x == 0x12345678) static_cast<int32_t *>(p.out)[lane] = x;
-        return;
-    }
-    conv_i8_epilogue<NB, (DBG & (32 | 64))>(p, acc, s_row + wave * 32, col0, lane);
-    if (DBG & 16) {
+    conv_i8_epilogue<NB>(p, acc, s_row + wave * 32, col0, lane);
+    if (STAMPS) {
         __builtin_amdgcn_s_waitcnt(0);                           // this wave's stores have been issued and acknowledged
         FPCC_I8_STAMP(39);
         if (wave == 0) {
@@ -1301,23 +1282,13 @@ int fpcc::conv_i8_run(const int8_t *a, int c_in, int lda, const int32_t *nbr, in
     // linear layers (identity map): the wave-per-block kernel reads 16 bytes of every 256-byte weight row per lane and spends ~3 us per
     // k-step on L1 refills whatever the row count (26-29 us for C -> 255 on a 300-row level); the tiled kernel stages W through LDS
     static const int linear_tiled_min = [] { const char *e = getenv("FPCC_I8_LINEAR_TILED_MIN"); return e ? atoi(e) : 1; }();
-    static const int tiled_dbg_env = [] { const char *e = getenv("FPCC_I8_DBG"); return e ? atoi(e) : 0; }();
-    const int tiled_dbg = g_i8_stamps_on ? 16 : tiled_dbg_env;
     const unsigned idx_bytes = (unsigned)n_offsets * 128u * 4u;             // the tiled kernel's slice of the kernel map in LDS
-    if (width > 64 && tiled && n_out >= 2048 && tiled_dbg) {
-        const dim3 grid(gx, (width + 127) / 128);
-        // the ablations profiles/r04/int8_conv.md cites: 1 no MFMA, 7 no MFMA / gather / W fetch, 8 no epilogue, 15 all of them
-        if (tiled_dbg == 1) hipLaunchKernelGGL((k_conv_i8_tiled<4, 1>), grid, dim3(256), idx_bytes, s, p);
-        else if (tiled_dbg == 8) hipLaunchKernelGGL((k_conv_i8_tiled<4, 8>), grid, dim3(256), idx_bytes, s, p);
-        else if (tiled_dbg == 15) hipLaunchKernelGGL((k_conv_i8_tiled<4, 15>), grid, dim3(256), idx_bytes, s, p);
-        else if (tiled_dbg == 16) hipLaunchKernelGGL((k_conv_i8_tiled<4, 16>), grid, dim3(256), idx_bytes, s, p);   // stamps, results exact
-        else if (tiled_dbg == 32) hipLaunchKernelGGL((k_conv_i8_tiled<4, 32>), grid, dim3(256), idx_bytes, s, p);   // epilogue computes, stores nothing
-        else if (tiled_dbg == 64) hipLaunchKernelGGL((k_conv_i8_tiled<4, 64>), grid, dim3(256), idx_bytes, s, p);   // epilogue stores, computes nothing
-        else hipLaunchKernelGGL((k_conv_i8_tiled<4, 7>), grid, dim3(256), idx_bytes, s, p);
+    if (width > 64 && tiled && n_out >= 2048 && g_i8_stamps_on) {              // stamps, results exact
+        hipLaunchKernelGGL((k_conv_i8_tiled<4, true>), dim3(gx, (width + 127) / 128), dim3(256), idx_bytes, s, p);
     } else if (width > 64 && tiled && n_out >= (nbr ? 2048 : linear_tiled_min)) {
         static const int tile_nb = [] { const char *e = getenv("FPCC_I8_NB"); return e ? atoi(e) : 4; }();
         static const int tile_mw = [] { const char *e = getenv("FPCC_I8_MW"); return e ? atoi(e) : 4; }();
-        if (tile_nb == 2 && tile_mw == 3) hipLaunchKernelGGL((k_conv_i8_tiled<2, 0, 3>), dim3(gx, (width + 63) / 64), dim3(256), idx_bytes, s, p);
+        if (tile_nb == 2 && tile_mw == 3) hipLaunchKernelGGL((k_conv_i8_tiled<2, false, 3>), dim3(gx, (width + 63) / 64), dim3(256), idx_bytes, s, p);
         else if (tile_nb == 2) hipLaunchKernelGGL((k_conv_i8_tiled<2>), dim3(gx, (width + 63) / 64), dim3(256), idx_bytes, s, p);
         else hipLaunchKernelGGL((k_conv_i8_tiled<4>), dim3(gx, (width + 127) / 128), dim3(256), idx_bytes, s, p);
     } else if (width > 64) {

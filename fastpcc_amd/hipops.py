@@ -498,6 +498,7 @@ def packed_weights(w: torch.Tensor, c1: int, c2: int, c_out: int, n_offsets: int
 
 
 KNOB_WAVE_ON, KNOB_WAVE_NBW, KNOB_WAVE_SB, KNOB_WAVE_DBG, KNOB_MFMA_TILE, KNOB_POINTWISE_ROWS = 0, 1, 2, 3, 5, 6
+# KNOB_WAVE_DBG: 0 = off, 16 = the stamped builds of the grouped and the LDS-operand kernel (results exact); anything else is refused
 KNOB_GROUPED_FOLD_ROWS = 4       # rows from which grouped (order 3) layers run folded on one wave per unit; 0 = never
 KNOB_GROUPED_OFF, KNOB_GROUPED_NBW, KNOB_WAVE22_ROWS = 7, 8, 9      # 7: experiments only (FPCC_EXPERIMENT=1), changes the summation order
 KNOB_PERSIST = 12     # workgroups per CU of the persistent grouped / folded kernels (0 = off)
@@ -524,8 +525,8 @@ def transpose_table(table: torch.Tensor, ld: int = 32) -> torch.Tensor:
 
 
 def conv_debug_stamps(buf: Optional[torch.Tensor]) -> None:
-    """diagnostic (fpcc_conv_debug_stamps): int64 device buffer the grouped kernel's waves leave their stage stamps in while knob 3
-    is 16; None detaches"""
+    """diagnostic (fpcc_conv_debug_stamps): int64 device buffer the waves of the grouped kernel (or, where knob 10 selects it, of the
+    LDS-operand kernel) leave their stage stamps in while knob 3 (KNOB_WAVE_DBG) is 16; results stay exact; None detaches"""
     if buf is None:
         _ok(lib().fpcc_conv_debug_stamps(None, 0))
     else:
@@ -541,7 +542,9 @@ def conv_i8_debug_stamps(buf: Optional[torch.Tensor]) -> None:
 
 
 def conv_set_tuning(which: int, value: int) -> int:
-    """process-wide tuning knob of the wave kernel (fpcc_conv_set_tuning); returns the previous value"""
+    """process-wide tuning knob of the wave kernel (fpcc_conv_set_tuning); returns the previous value.  No knob changes a result
+    (knob 7 apart, which needs FPCC_EXPERIMENT=1); a value a knob does not know -- knob 3 takes 0 and 16 only -- raises FpccError and
+    leaves the knob as it was"""
     before = _ok(lib().fpcc_conv_set_tuning(int(which), int(value)))
     conv_order.cache_clear()                    # knobs 4 / 7 (experiments only) move the summation-order thresholds
     return before

@@ -208,12 +208,13 @@ int fpcc_conv_f32(const float *x1, int c1, int ld1, const float *x2, int c2, int
  * the caller caches it next to the weights (fastpcc_amd/hipops.py keeps one per weight tensor). */
 int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int groups);
 /* Tuning knobs of the wave kernel (process-wide; initial values from FPCC_CONV_WAVE / FPCC_WAVE_NBW / FPCC_WAVE_SB).  None
- * changes a result -- the tests run every setting against the same oracle output.  Returns the previous value.
+ * changes a result (knob 7 apart, see there) -- the tests run every setting against the same oracle output.  Returns the previous value.
  *   0  use the wave kernel when packed weights are given (1) or the workgroup-tiled kernel (0)
  *   1  column blocks per wave: 0 = by map size, else 1 | 2 | 4
  *   2  1 = the next stage's address arithmetic may be scheduled between the MFMAs, 0 = nothing crosses the load points
- *   3  timing experiments only (results are WRONG): 1 = no gather traffic, 2 = weights from one chunk, 3 = both; 0 = off;
- *      16 = stage stamps of the grouped kernel (results exact, see fpcc_conv_debug_stamps)
+ *   3  0 = off; 16 = the stamped builds of the grouped kernel and of the LDS-operand kernel of knob 10 (results exact, see
+ *      fpcc_conv_debug_stamps; the LDS-operand kernel's stamps were value 32 before, 16 now selects them too).  No environment
+ *      variable.  Any other value is refused with FPCC_E_ARG and leaves the knob as it was.
  *   5  row tile of the workgroup-tiled kernel: 0 = by map size, 1 | 2 | 3 = 128 | 64 | 32 rows
  *   6  rows from which per-point layers (one offset, identity map) run on the persistent kernel that keeps the weights in
  *      registers (FPCC_POINTWISE_MIN_ROWS, default 32768); 0 = never

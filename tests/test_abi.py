@@ -32,6 +32,23 @@ def test_hip_library_exports_header():
     assert set(names) == set(hipops.HIP_SYMBOLS)
 
 
+def test_no_ablation_switch_in_the_shipped_library():
+    """the timing ablations (builds of the hot kernels whose results are wrong by construction) are not part of the product: neither of
+    the environment variables that selected them is known to libfpcc_hip.so or named in its sources and headers"""
+    import glob
+    names = (b'FPCC_WAVE_DBG', b'FPCC_I8_DBG')
+    blob = open(_build.HIP_LIB, 'rb').read()
+    for name in names:
+        assert name not in blob, name
+    files = [f for d in (os.path.join(ROOT, 'fastpcc_amd', 'csrc', 'hip'), os.path.join(ROOT, 'include'))
+             for ext in ('*.hip', '*.h') for f in glob.glob(os.path.join(d, ext))]
+    assert len(files) >= 10
+    for f in files:
+        text = open(f, 'rb').read()
+        for name in names:
+            assert name not in text, (f, name)
+
+
 def test_device_ops_fail_loudly_without_gpu():
     import pytest
     import torch

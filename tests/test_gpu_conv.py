@@ -566,6 +566,41 @@ def test_grouped_evaluation_is_order_3(ops, scene, c1, c2, c_out, n_off, nbw):
     assert (_bits(ordered.cpu().numpy()) == _bits(want)).all()
 
 
+def test_knob_3_takes_stamps_only_and_the_stamped_build_is_exact(ops, scene):
+    """knob 3 has two values: 0 and 16 (the stamped builds).  The values that once selected timing ablations -- builds whose results were
+    wrong by construction -- are refused and leave the knob as it was; under 16 with a stamp buffer attached a grouped shape of
+    test_grouped_evaluation_is_order_3 gives the oracle's order-3 bits and its waves leave their stamps"""
+    assert ops.conv_set_tuning(ops.KNOB_WAVE_DBG, 0) == 0
+    for v in (1, 2, 3, 4, 7, 17, 18, 19, 32, 64):
+        with pytest.raises(ops.FpccError):
+            ops.conv_set_tuning(ops.KNOB_WAVE_DBG, v)
+        assert ops.conv_set_tuning(ops.KNOB_WAVE_DBG, 0) == 0, v
+    c1, c_out, n_off = 128, 128, 27
+    rng = np.random.default_rng(c1 + c_out + n_off)
+    table = scene['k3']
+    n = table.shape[1]
+    x1 = rng.normal(size=(scene['lvl'].n, c1)).astype(np.float32)
+    w = (rng.normal(size=(n_off, c1, c_out)) / np.sqrt(n_off / 2 * c1)).astype(np.float32)
+    b = rng.normal(size=c_out).astype(np.float32)
+    slope = torch.tensor([0.25], device='cuda')
+    slots = 48                                                               # 64-bit words per wave (include/fpcc_hip.h)
+    stamps = torch.zeros(((n + 31) // 32) * (c_out // 32) * 4 * slots, dtype=torch.int64, device='cuda')   # four waves per unit, 32-column units
+    assert ops.conv_set_tuning(ops.KNOB_WAVE_DBG, 16) == 0
+    try:
+        ops.conv_debug_stamps(stamps)
+        assert ops.conv_order(c1, 0, c_out, n_off, 1, n) == 3
+        got = ops.conv_f32(_cuda(x1), _cuda(w), c_out, n, pack=True, nbr=_cuda(table), n_offsets=n_off, nbr_ks=n, nbr_os=1, bias=_cuda(b),
+                           act=ops.ACT_PRELU, slope=slope, clip=1.9)
+        torch.cuda.synchronize()
+    finally:
+        ops.conv_debug_stamps(None)
+        assert ops.conv_set_tuning(ops.KNOB_WAVE_DBG, 0) == 16
+    want = sc.conv_chain(x1, table, w, b, n, act=sc.ACT_PRELU, slope=0.25, clip=1.9, order=3)
+    assert (_bits(got.cpu().numpy()) == _bits(want)).all()
+    st = stamps.cpu().numpy().reshape(-1, slots)
+    assert (st[:, 0] != 0).any()                                             # the stamped build ran: [0] is s_memtime at kernel entry
+
+
 @pytest.mark.parametrize('c1,c2,c_out,n_off', [(128, 0, 128, 27), (128, 128, 128, 27), (64, 0, 64, 27), (64, 0, 128, 8), (32, 0, 32, 27), (96, 0, 32, 27)])
 @pytest.mark.parametrize('sparse', [False, True])
 def test_folded_evaluation_is_order_3_too(ops, scene, c1, c2, c_out, n_off, sparse):

@@ -43,7 +43,6 @@ cases = [('natural', None), ('pattern', order)]
 if os.environ.get('ONLY'):
     cases = [c for c in cases if c[0] == os.environ['ONLY']]
 variants = [(None, None)]
-DBG = [int(v) for v in os.environ.get('DBG', '0').split(',')]
 if os.environ.get('SWEEP'):
     variants = [(0, 0)] + [(nbw, sb) for nbw in (1, 2, 4) if nbw <= c_out // 32 for sb in (0, 1)]
 if os.environ.get('NBWS'):
@@ -59,8 +58,7 @@ if os.environ.get('LDS'):        # LDS=0,2,3,4: the default kernels (0) against 
     variants = [(-100 - int(v), 1) for v in os.environ['LDS'].split(',')]
 if os.environ.get('FORMS'):      # FORMS=1: the three forms of the order-3 evaluation -- four waves x 32 columns, four waves x 64 columns, folded
     variants = [(-201, 1), (-202, 1), (-203, 1)]
-for dbg, (nbw, sb) in [(a, c) for a in DBG for c in variants]:
-  ops.conv_set_tuning(3, dbg)
+for nbw, sb in variants:
   tag = ''
   if nbw is not None and nbw <= -201:
       ops.conv_set_tuning(ops.KNOB_GROUPED_FOLD_ROWS, 1 if nbw == -203 else 0)
@@ -72,7 +70,7 @@ for dbg, (nbw, sb) in [(a, c) for a in DBG for c in variants]:
       ops.conv_set_tuning(ops.KNOB_LDS_ROWS, 1 if rb else 0)
       if rb:
           ops.conv_set_tuning(ops.KNOB_LDS_ROW_BLOCKS, rb)
-      tag = f' [lds kernel, {rb} row blocks, dbg={dbg}]' if rb else f' [default kernel dbg={dbg}]'
+      tag = f' [lds kernel, {rb} row blocks]' if rb else ' [default kernel]'
       nbw = None
   if nbw is not None and nbw < 0:
       ops.conv_set_tuning(ops.KNOB_WAVE_ON, 1); ops.conv_set_tuning(ops.KNOB_WAVE_NBW, 0); ops.conv_set_tuning(ops.KNOB_WAVE_SB, sb)
@@ -85,7 +83,7 @@ for dbg, (nbw, sb) in [(a, c) for a in DBG for c in variants]:
       nbw = None
   if nbw is not None:
       ops.conv_set_tuning(ops.KNOB_WAVE_ON, int(nbw > 0)); ops.conv_set_tuning(ops.KNOB_WAVE_NBW, nbw); ops.conv_set_tuning(ops.KNOB_WAVE_SB, sb)
-      tag = f' [tiled kernel dbg={dbg}]' if nbw == 0 else f' [wave nbw={nbw} sb={sb} dbg={dbg}]'
+      tag = ' [tiled kernel]' if nbw == 0 else f' [wave nbw={nbw} sb={sb}]'
   for name, ro in cases:
     # MI355X's power management starts a burst of matrix work near 2.0 GHz and needs ~30 ms of uninterrupted load to reach 2.4 GHz
     # (profiles/r03/clock_ramp.md): without this warm-up whichever variant runs LAST looks 5-10 % faster than the first

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-wave phase times of k_conv_lds (knob 3 = 32: stamps; 60: stamps on the bare structure without DMAs, barrier and fragment reads).
+"""Per-wave phase times of k_conv_lds (knob 3 = 16: stamps).
 usage: lds_stamp_probe.py [level=1] [c_in=128] [c_out=128] [row_blocks=2]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,7 +31,7 @@ ops.conv_set_tuning(ops.KNOB_LDS_ROW_BLOCKS, rb)
 S = 48
 waves_per_wg = 2 * rb
 n_waves = ((n + 32 * rb - 1) // (32 * rb)) * waves_per_wg
-for dbg in (32, 60):
+for dbg in (16,):
     ops.conv_set_tuning(ops.KNOB_WAVE_DBG, dbg)
     buf = torch.zeros(n_waves * S, dtype=torch.int64, device='cuda')
     ops.conv_debug_stamps(buf)

@@ -44,7 +44,7 @@ for lv in levels:
     ref = run().clone()
     t_plain = timed()
     print(f'## level {lv}: {n} rows, {c_in}->{c_out}, 27 offsets; plain build {t_plain:.1f} us per launch (back to back, incl. launch gap)')
-    for dbg in (16, 17, 18, 19):
+    for dbg in (16,):
         ops.conv_set_tuning(ops.KNOB_WAVE_DBG, dbg)
         n_waves = ((n + 31) // 32) * (c_out // 32) * 4 * 2        # room for either column-group width
         buf = torch.zeros(n_waves * S, dtype=torch.int64, device='cuda')
@@ -64,7 +64,7 @@ for lv in levels:
         t0 = st[:, 0].min()
         span = (st[:, 42].max() - t0)
         mhz = 2400.0
-        label = {16: 'real operands', 17: 'no gather traffic (every row = row 0)', 18: 'weights of one chunk (vector L1)', 19: 'neither'}[dbg]
+        label = 'real operands'
         print(f'### dbg {dbg}: {label}; {len(st)} waves, stamped launch {t_st:.1f} us, first wave entry -> last store {span} cycles = {span / mhz:.1f} us at 2.4 GHz')
         d = lambda a, b: (st[:, b] - st[:, a])
         late = st[:, 0] - t0
