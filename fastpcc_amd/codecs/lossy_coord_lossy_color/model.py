@@ -1,5 +1,5 @@
 """Joint geometry + colour codec: module tree and frame layout of `PCC` in
-/root/reference/models/convolutional/lossy_coord_lossy_color/model.py:23-314 (inference).  Differences to lossy_coord_v2:
+/root/reference/models/convolutional/lossy_coord_lossy_color/model.py:23-314.  Differences to lossy_coord_v2:
 4-channel input (R, G, B in [0,1] and a constant 2), a 3-stage encoder to stride 4, a two-stage generative decoder whose
 last stage also predicts the colours, and every level of the lossless coder carries residual features."""
 import io
@@ -47,7 +47,7 @@ class PCC(nn.Module):
 
     def forward(self, pc_data: PCData):
         if self.training:
-            raise NotImplementedError('training is not part of this inference build')
+            return self.train_forward(pc_data.xyz, pc_data.color, pc_data.training_step, pc_data.batch_size)
         if pc_data.batch_size != 1:
             raise ValueError('Only supports batch size == 1 during testing.')
         return self.test_forward(pc_data)
@@ -65,6 +65,40 @@ class PCC(nn.Module):
                              quantization_mode=ME.SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE)
         cm.build_pyramid(pc.coordinate_map_key, len(self.cfg.encoder_channels) - 1 + sum(self.cfg.geo_lossl_if_sample))
         return pc
+
+    def train_forward(self, batched_coord: torch.Tensor, batched_color: torch.Tensor, training_step: int, batch_size: int) -> dict:
+        """rate + geometry + colour objective of one batch (model.py:167-214): {'loss': tensor with the autograd graph, every other
+        term detached, a 0-dim device tensor} -- the conventions of lossy_coord_v2.PCC.train_forward.  The engine keeps every map in
+        Morton order (the reference sorts only at test time); the input tensor's features follow that permutation, so the colour
+        target is read back from them in the row order of the target key."""
+        sparse_pc = self.get_sparse_pc(batched_coord, batched_color)
+        feature, points_num_list = self.encoder(sparse_pc)
+        bottleneck_feature, loss_dict = self.em_lossless_based(feature, batch_size)
+        target_rgb = sparse_pc.F[:, :3].detach().mul(255).round_()
+        for k, v in self.decoder(bottleneck_feature, points_num_list, sparse_pc.coordinate_map_key, target_rgb).items():
+            loss_dict[k] = loss_dict[k] + v if k in loss_dict else v
+        cfg = self.cfg
+        if training_step < cfg.warmup_fea_loss_steps:
+            step = (cfg.warmup_fea_loss_factor - cfg.bits_loss_factor) / cfg.warmup_fea_loss_steps
+            fea_factor = cfg.warmup_fea_loss_factor - step * training_step if cfg.linear_warmup else cfg.warmup_fea_loss_factor
+        else:
+            fea_factor = cfg.bits_loss_factor
+        if training_step < cfg.warmup_color_loss_steps:
+            step = (cfg.warmup_color_loss_factor - cfg.color_recon_loss_factor) / cfg.warmup_color_loss_steps
+            color_factor = cfg.warmup_color_loss_factor - step * training_step if cfg.linear_warmup else cfg.warmup_color_loss_factor
+        else:
+            color_factor = cfg.color_recon_loss_factor
+        for key in loss_dict:
+            if key.endswith('bits_loss'):
+                loss_dict[key] = loss_dict[key] * (fea_factor if 'fea' in key else cfg.bits_loss_factor)
+            if key.startswith('coord_') and key.endswith('_recon_loss'):
+                loss_dict[key] = loss_dict[key] * cfg.coord_recon_loss_factor
+        loss_dict['color_recon_loss'] = loss_dict['color_recon_loss'] * color_factor
+        loss_dict['loss'] = sum(loss_dict.values())
+        for key in loss_dict:
+            if key != 'loss':
+                loss_dict[key] = loss_dict[key].detach()
+        return loss_dict
 
     @hipops.no_gc_pause
     @torch.no_grad()

@@ -7,39 +7,12 @@
 // touch its own block are contiguous key ranges; every point outside them is farther than 2^l + 1 along some axis, so
 // the search ends at the first level whose best squared distance is <= (2^l + 1)^2.  Integer arithmetic throughout.
 #include "common.h"
+#include "voxel_search.h"
 
 #include <algorithm>
 
 namespace fpcc {
 namespace {
-
-__device__ __forceinline__ uint64_t m_spread21(uint32_t v) {
-    uint64_t x = v & 0x1fffffu;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-__device__ __forceinline__ uint32_t m_gather21(uint64_t x) {
-    x &= 0x1249249249249249ull;
-    x = (x ^ (x >> 2)) & 0x10c30c30c30c30c3ull;
-    x = (x ^ (x >> 4)) & 0x100f00f00f00f00full;
-    x = (x ^ (x >> 8)) & 0x1f0000ff0000ffull;
-    x = (x ^ (x >> 16)) & 0x1f00000000ffffull;
-    x = (x ^ (x >> 32)) & 0x1fffffull;
-    return static_cast<uint32_t>(x);
-}
-
-__device__ __forceinline__ int64_t lower_bound(const int64_t *__restrict__ keys, int64_t n, int64_t want) {
-    int64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (keys[mid] < want) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void k_nn_dist2(const int64_t *__restrict__ keys, int64_t m, int bits,
                                                   const int32_t *__restrict__ query, int64_t n,
@@ -144,36 +117,7 @@ __global__ __launch_bounds__(256) void k_knn3d(const float *__restrict__ p1, int
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Point-to-plane (D2) and Hausdorff distortion: what the reference obtains from `pc_error -n <normals> --hausdorff=1`
 // (/root/reference/lib/metrics/pc_error_wrapper.py:40-76; normals from the PLY file or Open3D's estimate_normals, :57-72).
-// Everything works on SORTED Morton key sets like k_nn_dist2; rows are indexes into those sorted sets.
-
-struct Blocks27 {                    // the 27 blocks of edge 2^l around a query: contiguous key ranges
-    int64_t prefix;
-    int32_t side;
-    int4 q;
-    __device__ Blocks27(int4 q_, int bits) : prefix((int64_t)q_.x << (3 * bits)), side(1 << bits), q(q_) {}
-    template <class F>
-    __device__ __forceinline__ void scan(const int64_t *__restrict__ keys, int64_t m, int bits, int l, F &&f) const {
-        const int64_t morton_mask = ((int64_t)1 << (3 * bits)) - 1;
-        const int32_t nblk = side >> l;
-        const int32_t bx = min(max(q.y, 0), side - 1) >> l, by = min(max(q.z, 0), side - 1) >> l, bz = min(max(q.w, 0), side - 1) >> l;
-        for (int dz = -1; dz <= 1; ++dz)
-            for (int dy = -1; dy <= 1; ++dy)
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const int32_t cx = bx + dx, cy = by + dy, cz = bz + dz;
-                    if (cx < 0 || cy < 0 || cz < 0 || cx >= nblk || cy >= nblk || cz >= nblk) continue;
-                    const int64_t first = prefix | (int64_t)((m_spread21(cx) | m_spread21(cy) << 1 | m_spread21(cz) << 2) << (3 * l));
-                    const int64_t last = first + ((int64_t)1 << (3 * l));
-                    for (int64_t r = lower_bound(keys, m, first); r < m; ++r) {
-                        int64_t k = keys[r];
-                        if (k >= last) break;
-                        k &= morton_mask;
-                        const int64_t ex = (int64_t)m_gather21((uint64_t)k) - q.y, ey = (int64_t)m_gather21((uint64_t)k >> 1) - q.z,
-                                      ez = (int64_t)m_gather21((uint64_t)k >> 2) - q.w;
-                        f(r, ex, ey, ez, ex * ex + ey * ey + ez * ez);
-                    }
-                }
-    }
-};
+// Everything works on SORTED Morton key sets like k_nn_dist2 (block search: voxel_search.h); rows are indexes into those sorted sets.
 
 // The K nearest voxels of every query, ordered by (squared distance, row): the order is total, so the result is unique.  A level is
 // final when K candidates are STRICTLY nearer than 2^l + 1 -- every voxel outside the 27 blocks is at least that far along one axis.

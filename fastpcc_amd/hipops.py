@@ -58,6 +58,9 @@ _SIGS = {
     'fpcc_transfer_normals_ws_bytes': (_i64, [_i64, _i64]),
     'fpcc_transfer_normals': (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
     'fpcc_sum_max_f64': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    'fpcc_recolor_ws_bytes': (_i64, [_i64]),
+    'fpcc_recolor': (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
+    'fpcc_keys_member': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
     'fpcc_transpose_weights_f32': (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     'fpcc_conv_wgrad_ws_bytes': (_i64, [_i32, _i32, _i32, _i32, _i64]),
     'fpcc_conv_wgrad_f32': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp,
@@ -870,6 +873,31 @@ def sum_max_f64(values: torch.Tensor) -> torch.Tensor:
     out = torch.empty(2, dtype=torch.float64, device=values.device)
     ws = torch.empty(max(2 * ((n + 4095) // 4096), 2), dtype=torch.float64, device=values.device)
     _ok(lib().fpcc_sum_max_f64(_dev(values, torch.float64, 'values', n == 0), n, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()))
+    return out
+
+
+def recolor(pred_keys: torch.Tensor, tgt_keys: torch.Tensor, tgt_rgb: torch.Tensor, bits: int) -> torch.Tensor:
+    """float32 [m, 3]: the colour every kept reconstructed voxel (sorted unique `pred_keys`) takes from the original cloud (sorted unique
+    `tgt_keys` with colours `tgt_rgb` float32 [n, 3] in row order), by nearest-voxel search in both directions per sample
+    (fpcc_recolor; colours must be finite and within [-1024, 1024]).  Deterministic: two calls give the same bits."""
+    m, n = pred_keys.shape[0], tgt_keys.shape[0]
+    if tgt_rgb.dim() != 2 or tuple(tgt_rgb.shape) != (n, 3):
+        raise ValueError('tgt_rgb must be float32 [n, 3], one row per target key')
+    out = torch.empty((m, 3), dtype=torch.float32, device=tgt_keys.device)
+    L = lib()
+    need = _ok(L.fpcc_recolor_ws_bytes(m))
+    ws = torch.empty(max(need // 8, 2), dtype=torch.int64, device=tgt_keys.device)
+    _ok(L.fpcc_recolor(_dev(pred_keys, torch.int64, 'pred_keys', m == 0), m, _dev(tgt_keys, torch.int64, 'tgt_keys', n == 0), n,
+                       _dev(tgt_rgb, torch.float32, 'tgt_rgb', n == 0), bits, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()))
+    return out
+
+
+def keys_member(keys: torch.Tensor, query: torch.Tensor) -> torch.Tensor:
+    """int32 [n]: the row of every query key in the sorted unique key set `keys`, -1 where it is not a member (fpcc_keys_member)"""
+    n = query.shape[0]
+    out = torch.empty(n, dtype=torch.int32, device=query.device)
+    _ok(lib().fpcc_keys_member(_dev(keys, torch.int64, 'keys', keys.numel() == 0), keys.shape[0], _dev(query, torch.int64, 'query', n == 0), n,
+                               out.data_ptr(), _stream()))
     return out
 
 

@@ -165,6 +165,40 @@ def shapenet_like(seed: int, resolution: int = 128, points: int = 200000) -> np.
     return np.unique(np.minimum((p * (resolution - 1)).round().astype(np.int32), resolution - 1), axis=0)
 
 
+def smooth_colors(xyz: np.ndarray, seed: int, resolution: int = 128) -> np.ndarray:
+    """uint8 [n, 3]: a smooth seeded colour field (a few low-frequency waves per channel) sampled on the voxels `xyz`, so that
+    neighbouring voxels of a surface have similar colours, as the textures of scanned objects do"""
+    rng = np.random.default_rng(seed + 7919)
+    p = xyz.astype(np.float64) / resolution
+    rgb = np.full((len(xyz), 3), 127.5)
+    for c in range(3):
+        for _ in range(3):
+            k = rng.normal(size=3) * rng.uniform(1.0, 4.0)
+            rgb[:, c] += rng.uniform(20, 45) * np.sin(2 * np.pi * (p @ k) + rng.uniform(0, 2 * np.pi))
+    return np.clip(np.round(rgb), 0, 255).astype(np.uint8)
+
+
+def synthetic_color_batches(rank: int, world: int, cfg: TrainConfig, device: torch.device, resolution: int = 128,
+                            first_seed: int = 10, pool: int = 16) -> Iterator[PCData]:
+    """synthetic_batches with colours (the input of lossy_coord_lossy_color): the same clouds, a smooth colour field on each"""
+    if cfg.batch_size % world:
+        raise ValueError(f'global batch {cfg.batch_size} does not divide over {world} ranks')
+    per_rank = cfg.batch_size // world
+    seeds = list(range(first_seed + rank, first_seed + max(pool, cfg.batch_size), world))
+    clouds = [shapenet_like(s, resolution) for s in seeds]
+    colors = [smooth_colors(xyz, s, resolution) for xyz, s in zip(clouds, seeds)]
+    at = 0
+    while True:
+        rows, rgb = [], []
+        for b in range(per_rank):
+            xyz = clouds[(at + b) % len(clouds)]
+            rows.append(np.concatenate((np.full((len(xyz), 1), b, np.int32), xyz), 1))
+            rgb.append(colors[(at + b) % len(clouds)])
+        at += per_rank
+        yield PCData(xyz=torch.from_numpy(np.concatenate(rows)).to(device), color=torch.from_numpy(np.concatenate(rgb)).to(device),
+                     batch_size=per_rank, resolution=[resolution] * per_rank)
+
+
 def synthetic_batches(rank: int, world: int, cfg: TrainConfig, device: torch.device, resolution: int = 128,
                       first_seed: int = 10, pool: int = 16) -> Iterator[PCData]:
     """endless stream of this rank's share (batch_size / world clouds) of the global batches"""

@@ -512,6 +512,26 @@ int fpcc_transfer_normals(const int64_t *keys_a, int64_t n_a, const int32_t *coo
                           int64_t n_b, const int32_t *coords_b, int bits, double *normals_b_out, void *ws, int64_t ws_bytes, void *stream);
 int fpcc_sum_max_f64(const double *values, int64_t n, double *sum_max_out, void *ws, int64_t ws_bytes, void *stream);
 
+/* Recolouring target of the colour codec's training loss -- replaces `sample_wise_recolor`, a knn3d search in both directions plus
+ * masked tensor ops (models/convolutional/lossy_coord_lossy_color/layers.py:269-333).  pred_keys: the m kept reconstructed voxels,
+ * tgt_keys: the n original voxels, both SORTED unique key sets of `bits` bits per axis with the sample index above the Morton bits
+ * (a sample never sees another sample's voxels); tgt_rgb float [n][3] in row order; rgb_out float [m][3].  With K = 8 and "the K
+ * nearest" = the first K in the order (squared distance, row) of fpcc_knn_voxels:
+ *   - an original voxel whose K nearest kept voxels include one at distance 0 gives that voxel its colour, bit for bit, and nothing else;
+ *   - every other original voxel adds rgb / sqrt(d) to the numerator and 1 / sqrt(d) to the denominator of those of its K nearest kept
+ *     voxels that lie at its minimum squared distance d;
+ *   - a kept voxel without exact match and with a nonzero denominator gets numerator / denominator;
+ *   - a kept voxel that received nothing gets the plain mean colour of those of its own K nearest original voxels that lie at the
+ *     minimum distance (0 where its sample holds no original voxel).
+ * Sums are integers (2^-52 fixed point in 96-bit accumulators): independent of the order of the atomics, two runs give the same bits.
+ * Accepted colours: finite, |value| <= 1024; anything else returns FPCC_E_ARG (the call waits for the stream to learn it).
+ * ws: caller-owned, 16-byte aligned, fpcc_recolor_ws_bytes(m) bytes.
+ * fpcc_keys_member: row_out[i] = the row of query[i] in the SORTED unique key set `keys`, or -1 (binary search). */
+int64_t fpcc_recolor_ws_bytes(int64_t m);
+int fpcc_recolor(const int64_t *pred_keys, int64_t m, const int64_t *tgt_keys, int64_t n, const float *tgt_rgb, int bits,
+                 float *rgb_out, void *ws, int64_t ws_bytes, void *stream);
+int fpcc_keys_member(const int64_t *keys, int64_t m, const int64_t *query, int64_t n, int32_t *row_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Integer-only pipeline (lossl_coord_int).  Replaces the pybind module `int_sparse_conv_ext`                      */
 /* (lib/int_sparse_conv/src/binding.cu:114-145).  All arithmetic is exact: results are order independent.          */
