@@ -162,20 +162,10 @@ class Decoder(nn.Module):
         edges = cm.batch_offsets(parent)
         if len(target) != len(edges) - 1:
             raise ValueError('one pruning target per sample expected')
-        cell = top_edges = None
+        cell = None
         if parent is not top:
-            cell = cm._ancestor_rows(parent, top).to(torch.int32)
-            top_edges = cm.batch_offsets(top)
-        keep = []
-        for c, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
-            if not 8 * (b - a) > target[c]:
-                raise ValueError('fewer candidates than points to keep')
-            if cell is None:
-                keep.append(ops.topk_keep(logits[8 * a: 8 * b], int(target[c])))
-            else:
-                keep.append(ops.topk_keep_cells(logits[8 * a: 8 * b], (cell[a:b] - top_edges[c]).contiguous(),
-                                                top_edges[c + 1] - top_edges[c], int(target[c])))
-        return torch.cat(keep)
+            cell = cm._ancestor_rows(parent, top).to(torch.int32).contiguous()
+        return ops.topk_keep_batch(logits, edges, target, cell, 0 if cell is None else top.n)
 
     @torch.no_grad()
     def test_forward(self, fea, points_num_list) -> ME.SparseTensor:

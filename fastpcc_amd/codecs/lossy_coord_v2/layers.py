@@ -3,8 +3,9 @@
 Same class names, constructor arguments and sub-module attribute names as
 /root/reference/models/convolutional/lossy_coord_v2/layers.py:28-415, so a reference checkpoint's state_dict keys load
 unchanged; the forward passes are written against fastpcc_amd.engine (fused conv+bias+activation(+clip) launches, lazy
-channel concatenation, fused top-k pruning).  Training-time members of the reference (`train_forward`, `get_target`,
-`get_coord_recon_loss`, `BoundFunction.backward`) are outside this inference path.
+channel concatenation, fused top-k pruning).  `Decoder.train_forward` trains any number of generative stages (every
+`baseline_r*` configuration); the ranking of a batch's candidates, training and inference, is one segmented call
+(hipops.topk_keep_batch).
 """
 from typing import List, Optional, Tuple
 
@@ -113,14 +114,17 @@ class Decoder(nn.Module):
 
     def train_forward(self, fea, points_num_list, target_key: ME.CoordinateMapKey) -> dict:
         """per upsampling stage: binary cross-entropy of the occupancy logits against the true finer coordinates, then
-        prune to (adaptive top-k | true) candidates (layers.py:118-137)"""
+        prune to (adaptive top-k | true) candidates (layers.py:118-137).  `coord_{i}_recon_loss` is the stage that generates the
+        candidates of tensor stride 2^i and is weighted by points_num_list[i] (both finest first), as in the reference."""
         loss = {}
         n_stage = len(self.upsample_blocks)
+        cm = fea.coordinate_manager
+        top = cm._map(fea.coordinate_map_key)      # local maxima are taken inside the voxels of this level
         inv = [1 / sum(c) for c in points_num_list] if points_num_list is not None else None
         for i, (up, classify) in enumerate(zip(self.upsample_blocks, self.classify_blocks)):
             fea = up(fea)
             pred = classify(fea)
-            keep = self.get_keep_train(pred, points_num_list)
+            keep = self.get_keep_train(pred, points_num_list, top)
             target = self.get_target(pred, target_key)
             keep |= target
             loss[f'coord_{n_stage - i - 1}_recon_loss'] = F.binary_cross_entropy_with_logits(
@@ -135,33 +139,41 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     def get_target(self, pred: ME.SparseTensor, target_key: ME.CoordinateMapKey) -> torch.Tensor:
-        """bool [n]: which generated candidates are voxels of the (strided) target set (layers.py:182-190)"""
+        """bool [n]: which generated candidates are voxels of the (strided) target set (layers.py:182-190).  Candidates generated
+        from the target's own parent map (the first stage): the target's child table says it.  Candidates under a PRUNED map (every
+        later stage): membership of their keys in the target's sorted keys.  `last_target_path` names the path taken."""
         cm = pred.coordinate_manager
         gen = cm._map(pred.coordinate_map_key)
         tgt = cm._map(cm.stride(target_key, pred.tensor_stride))
-        if not gen.generated or tgt.parent is not gen.parent:
-            raise NotImplementedError('the target set must be a child map of the map the candidates were generated from')
-        return ops.child_mask(tgt.child_row).bool()
+        if gen.generated and tgt.parent is gen.parent:
+            self.last_target_path = 'child_table'
+            return ops.child_mask(tgt.child_row).bool()
+        if gen.level != tgt.level or gen.bits != tgt.bits:
+            raise ValueError('candidates and strided target set differ in tensor stride')
+        self.last_target_path = 'keys_member'
+        return ops.keys_member(cm._keys(tgt), cm._keys(gen)) >= 0
 
     @torch.no_grad()
-    def get_keep_train(self, pred: ME.SparseTensor, points_num_list: Optional[List[List[int]]]) -> torch.Tensor:
-        """training-time variant of get_keep for a batch: per sample, the logits above its own k-th value, or the maximum
-        of their 2x2x2 cell.  Bookkeeping under no_grad, written with tensor ops (one stage of upsampling)."""
+    def get_keep_train(self, pred: ME.SparseTensor, points_num_list: Optional[List[List[int]]], top) -> torch.Tensor:
+        """get_keep for a training batch, any number of stages: every sample's candidates are ranked among themselves against the
+        sample's own target count (layers.py:164-174) in one segmented call; cells are the voxels of the decoder's input level `top`
+        (the 8 siblings in the first stage), as at inference."""
         cm = pred.coordinate_manager
         gen = cm._map(pred.coordinate_map_key)
-        if not gen.generated or len(self.upsample_blocks) != 1:
-            raise NotImplementedError('training-time pruning supports one generative stage (decoder_channels of length 1)')
-        logits = pred.F.view(-1, 8)
+        if not gen.generated:
+            raise NotImplementedError('get_keep expects the candidates of a generative upsampling')
+        parent = gen.parent
+        logits = pred.F.detach().reshape(-1).contiguous()
+        cell = None
+        if parent is not top:
+            cell = cm._ancestor_rows(parent, top).to(torch.int32).contiguous()
         if points_num_list is None:
-            return ((logits > 0) | (logits == logits.max(1, keepdim=True).values)).view(-1)
+            return fixed_keep(logits, cell, 0 if cell is None else top.n).bool()
         targets = points_num_list.pop()
-        edges = cm.batch_offsets(gen.parent)
-        keep = torch.empty(logits.numel(), dtype=torch.uint8, device=logits.device)
-        for tgt, a, b in zip(targets, edges[:-1], edges[1:]):
-            if not (b - a) * 8 > tgt:
-                raise ValueError('fewer candidates than points to keep')
-            keep[8 * a: 8 * b] = ops.topk_keep(logits[a:b].reshape(-1), int(tgt))      # the sample's own k-th value
-        return keep.bool()
+        edges = cm.batch_offsets(parent)
+        if len(targets) != len(edges) - 1:
+            raise ValueError('one pruning target per sample expected')
+        return ops.topk_keep_batch(logits, edges, targets, cell, 0 if cell is None else top.n).bool()
 
     @torch.no_grad()
     def test_forward(self, fea, points_num_list, coord_offset: Optional[torch.Tensor] = None):
@@ -212,16 +224,20 @@ class Decoder(nn.Module):
                 cell, m = m.parent_of[cell.long()], m.parent
             cell = cell.to(torch.int32).contiguous()
         if points_num_list is None:
-            # adaptive_pruning = False (layers.py:176-180): fixed threshold 0, plus the maximum of every cell
-            if cell is None:
-                cells = pred.F.view(-1, 8)
-                return ((cells > 0) | (cells == cells.max(1, keepdim=True).values)).view(-1).to(torch.uint8)
-            per_group = pred.F.view(-1, 8).max(1).values
-            cell_max = torch.full((top.n,), float('-inf'), dtype=per_group.dtype, device=per_group.device)
-            cell_max.scatter_reduce_(0, cell.long(), per_group, reduce='amax', include_self=True)
-            cells = pred.F.view(-1, 8)
-            return ((cells > 0) | (cells == cell_max[cell.long()][:, None])).view(-1).to(torch.uint8)
+            return fixed_keep(logits, cell, 0 if cell is None else top.n)
         return adaptive_keep(cm, parent, top, logits, cell, points_num_list.pop())
+
+
+def fixed_keep(logits: torch.Tensor, cell: Optional[torch.Tensor], n_cells: int) -> torch.Tensor:
+    """uint8 [8 m]: adaptive_pruning = False (layers.py:176-180) -- fixed threshold 0, plus the maximum of every cell (`cell`: the cell
+    of every group of 8 candidates; None = the group itself)"""
+    groups = logits.view(-1, 8)
+    per_group = groups.max(1).values
+    if cell is None:
+        return ((groups > 0) | (groups == per_group[:, None])).view(-1).to(torch.uint8)
+    cell_max = torch.full((n_cells,), float('-inf'), dtype=per_group.dtype, device=per_group.device)
+    cell_max.scatter_reduce_(0, cell.long(), per_group, reduce='amax', include_self=True)
+    return ((groups > 0) | (groups == cell_max[cell.long()][:, None])).view(-1).to(torch.uint8)
 
 
 def adaptive_keep(cm, parent, top, logits: torch.Tensor, cell: Optional[torch.Tensor], target: List[int]) -> torch.Tensor:
@@ -232,17 +248,8 @@ def adaptive_keep(cm, parent, top, logits: torch.Tensor, cell: Optional[torch.Te
         edges = cm.batch_offsets(parent)
         if len(target) != len(edges) - 1:
             raise ValueError('one pruning target per cloud expected')
-        top_edges = cm.batch_offsets(top) if cell is not None else None
-        keep = []
-        for c, (a, b) in enumerate(zip(edges[:-1], edges[1:])):
-            if not 8 * (b - a) > target[c]:
-                raise ValueError('fewer candidates than points to keep')
-            if cell is None:
-                keep.append(ops.topk_keep(logits[8 * a: 8 * b], target[c]))
-            else:
-                keep.append(ops.topk_keep_cells(logits[8 * a: 8 * b], (cell[a:b] - top_edges[c]).contiguous(),
-                                                top_edges[c + 1] - top_edges[c], target[c]))
-        return torch.cat(keep)
+        # one segmented select for all clouds (rows of `top` are cloud-major: the global cell ids never span two clouds)
+        return ops.topk_keep_batch(logits, edges, target, cell, 0 if cell is None else top.n)
     if len(target) != 1:
         raise NotImplementedError('batch size 1 at test time, as in the reference (model.py:121)')
     if not logits.numel() > target[0]:

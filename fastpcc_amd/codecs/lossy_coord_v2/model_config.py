@@ -72,7 +72,12 @@ def _load_with_includes(path: str):
             break
         inc = line[len('# include'):].strip().strip('"\'')
         if not os.path.isabs(inc):
-            inc = os.path.join(os.path.dirname(path), inc)
+            # the reference names its includes from the project root (its working directory): the first directory on the way up from
+            # the including file under which the path exists
+            base = os.path.dirname(os.path.abspath(path))
+            while not os.path.isfile(os.path.join(base, inc)) and os.path.dirname(base) != base:
+                base = os.path.dirname(base)
+            inc = os.path.join(base, inc)
         out.extend(_load_with_includes(inc))
     out.append(yaml.safe_load(text) or {})
     return out
@@ -88,3 +93,17 @@ BASELINE_R1 = dict(
 def baseline_r1() -> ModelConfig:
     """config/convolutional/lossy_coord_v2/baseline_r1.yaml:2-13, the configuration BASELINE.json's metric is quoted on."""
     return ModelConfig(**BASELINE_R1)
+
+
+def baseline_r3() -> ModelConfig:
+    """config/convolutional/lossy_coord_v2/baseline_r3.yaml:3-9 over baseline_r1: two generative decoder stages (tensor stride 4 -> 1)"""
+    return ModelConfig(**{**BASELINE_R1, **dict(
+        skip_encoding_fea=-1, encoder_channels=(16, 64, 128), decoder_channels=(64, 16), geo_lossl_if_sample=(0, 1) * 5,
+        geo_lossl_channels=(128,) * 10 + (1,), bits_loss_factor=0.8)})
+
+
+def baseline_r5() -> ModelConfig:
+    """config/convolutional/lossy_coord_v2/baseline_r5.yaml:3-10 over baseline_r1: three generative decoder stages (tensor stride 8 -> 1)"""
+    return ModelConfig(**{**BASELINE_R1, **dict(
+        skip_encoding_fea=-1, encoder_channels=(16, 64, 128, 128), decoder_channels=(128, 64, 16), geo_lossl_if_sample=(0, 1) * 4,
+        geo_lossl_channels=(128,) * 8 + (1,), bits_loss_factor=1.2, warmup_fea_loss_steps=10000)})

@@ -89,6 +89,26 @@ struct SelectState {
 };
 constexpr int kSelBins = 2048;
 
+// the counting loop of a pass, shared by the single and the batch kernel: workgroup blockIdx.x of gridDim.x strides over the groups
+// [p0, p1) and counts, in its LDS bins, the keys whose higher bits equal `prefix`.  A candidate that is its cell's maximum ranks as +inf.
+// PASS 0: bits 31..21, PASS 1: bits 20..10 under an 11-bit prefix, PASS 2: bits 9..0 under a 22-bit prefix
+template <int PASS, bool SEG>
+__device__ __forceinline__ void select_count(unsigned *s_h, const float4 *__restrict__ logit, int64_t p0, int64_t p1,
+                                             const int32_t *__restrict__ seg, const unsigned *__restrict__ seg_max, unsigned prefix) {
+    constexpr int kShift = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
+    constexpr unsigned kMask = PASS == 2 ? 1023u : 2047u;
+    for (int64_t p = p0 + (int64_t)blockIdx.x * 256 + threadIdx.x; p < p1; p += (int64_t)gridDim.x * 256) {
+        const float4 a = logit[2 * p], b = logit[2 * p + 1];
+        const float mx = SEG ? ord2f(seg_max[seg[p]]) : max8(a, b);
+        const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned key = f2ord(v[k] == mx ? __builtin_huge_valf() : v[k]);
+            if (PASS == 0 || (key >> (kShift + (PASS == 2 ? 10 : 11))) == prefix) atomicAdd(&s_h[(key >> kShift) & kMask], 1u);
+        }
+    }
+}
+
 // one pass: histogram of the key bits [kShift, kShift + 11) (10 in the last pass) of the candidates whose higher bits equal the prefix
 // found so far.  PASS 0 takes the rank as an argument.  One workgroup per CU at most: every workgroup merges its bins into the global
 // histogram with atomics, and on real logits most candidates share a few dozen bins (sign + exponent) -- ~12 ns per atomic on one address.
@@ -101,37 +121,18 @@ __global__ __launch_bounds__(256) void k_select_hist(const float4 *__restrict__ 
     __syncthreads();
     const unsigned long long rank = PASS ? st->rank : rank0;
     const unsigned prefix = PASS ? st->prefix : 0u;
-    // PASS 0: bits 31..21, PASS 1: bits 20..10 under an 11-bit prefix, PASS 2: bits 9..0 under a 22-bit prefix
-    constexpr int kShift = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
-    constexpr unsigned kMask = PASS == 2 ? 1023u : 2047u;
-    if (rank != 0ull)
-        for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < m; p += (int64_t)gridDim.x * 256) {
-            const float4 a = logit[2 * p], b = logit[2 * p + 1];
-            const float mx = SEG ? ord2f(seg_max[seg[p]]) : max8(a, b);
-            const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-            for (int k = 0; k < 8; ++k) {
-                const unsigned key = f2ord(v[k] == mx ? __builtin_huge_valf() : v[k]);
-                if (PASS == 0 || (key >> (kShift + (PASS == 2 ? 10 : 11))) == prefix) atomicAdd(&s_h[(key >> kShift) & kMask], 1u);
-            }
-        }
+    if (rank != 0ull) select_count<PASS, SEG>(s_h, logit, 0, m, seg, seg_max, prefix);
     __syncthreads();
     for (int i = threadIdx.x; i < kSelBins; i += 256)
         if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
 }
 
-// one workgroup after each pass (its own launch: the kernel boundary is what orders it behind every workgroup's atomics -- a
-// last-arriver scheme inside the pass kernel raced on this hardware and a device-scope fence per workgroup cost ~50 us): finds the bin
-// that holds the wanted rank by a scan over 256 chunk sums, extends the prefix, clears the bins for the next pass
+// the bin walk of a pass, shared by the single and the batch kernel (one workgroup of 256 on one set of 2048 bins): an inclusive scan
+// of the 256 chunk sums, then the one thread whose chunk holds the rank walks its 8 bins, extends the prefix and leaves the rank still to
+// find; every thread clears its bins for the next pass.  rank >= 1.
 template <int PASS>
-__global__ __launch_bounds__(256) void k_select_pick(unsigned *__restrict__ hist, SelectState *__restrict__ st, unsigned long long rank0) {
-    __shared__ unsigned long long s_part[256];
-    const unsigned long long rank = PASS ? st->rank : rank0;
-    const unsigned prefix = PASS ? st->prefix : 0u;
-    if (rank == 0ull) {                                                         // no threshold: everything above -inf is kept
-        if (threadIdx.x == 0) { st->rank = 0ull; if (PASS == 2) st->thr = -__builtin_huge_valf(); }
-        return;
-    }
+__device__ __forceinline__ void select_walk(unsigned *__restrict__ hist, SelectState *__restrict__ st, unsigned long long rank,
+                                            unsigned prefix, unsigned long long *s_part) {
     unsigned h8[8];                                                              // 8 bins per thread, ascending
 #pragma unroll
     for (int j = 0; j < 8; ++j) h8[j] = hist[threadIdx.x * 8 + j];
@@ -169,6 +170,21 @@ __global__ __launch_bounds__(256) void k_select_pick(unsigned *__restrict__ hist
     for (int j = 0; j < 8; ++j) hist[threadIdx.x * 8 + j] = 0;                  // clean for the next pass
 }
 
+// one workgroup after each pass (its own launch: the kernel boundary is what orders it behind every workgroup's atomics -- a
+// last-arriver scheme inside the pass kernel raced on this hardware and a device-scope fence per workgroup cost ~50 us): finds the bin
+// that holds the wanted rank by a scan over 256 chunk sums, extends the prefix, clears the bins for the next pass
+template <int PASS>
+__global__ __launch_bounds__(256) void k_select_pick(unsigned *__restrict__ hist, SelectState *__restrict__ st, unsigned long long rank0) {
+    __shared__ unsigned long long s_part[256];
+    const unsigned long long rank = PASS ? st->rank : rank0;
+    const unsigned prefix = PASS ? st->prefix : 0u;
+    if (rank == 0ull) {                                                         // no threshold: everything above -inf is kept
+        if (threadIdx.x == 0) { st->rank = 0ull; if (PASS == 2) st->thr = -__builtin_huge_valf(); }
+        return;
+    }
+    select_walk<PASS>(hist, st, rank, prefix, s_part);
+}
+
 template <bool SEG>
 __global__ void k_keep_thr(const float4 *__restrict__ logit, int64_t m, const int32_t *__restrict__ seg, const unsigned *__restrict__ seg_max,
                            const SelectState *__restrict__ st, uint8_t *__restrict__ keep) {
@@ -202,6 +218,110 @@ int select_and_keep(const float *logit, int64_t m, const int32_t *seg, const uns
     hipLaunchKernelGGL(k_select_pick<2>, dim3(1), dim3(256), 0, s, hist, st, 0ull);
     hipLaunchKernelGGL(k_keep_thr<SEG>, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, s, lg, m, seg, seg_max, (const SelectState *)st, keep_out);
     return check_hip(hipGetLastError(), "topk select");
+}
+
+// ---- the same select for MANY segments (the clouds of a batch) in one set of launches ---------------------------------------------------
+// Only the threshold is a segment's own: the k-th smallest of ITS candidates (rank = 8 * groups - target).  Every kernel above has a twin
+// whose second grid dimension (histogram passes, bin walk) or a search of the segment edges (final mask) names the segment; bins and
+// select states are per segment ([n_seg][2048], [n_seg]).  Launches: as many as for one segment, whatever n_seg.  Cell ids are global and
+// a cell lies inside one segment, so k_seg_max serves unchanged.  A segment's mask is what the single call gives on it alone: the same
+// keys, the same order statistic, the same comparison.
+constexpr int kMaxSegments = 256;      // FPCC_TOPK_BATCH_MAX_SEGMENTS: the final mask keeps the edges in LDS (2 KB), grid.y of the passes
+
+// rank still to find in segment s before the first pass (0 = no threshold: the target is not below the candidate count)
+__device__ __forceinline__ unsigned long long first_rank(int64_t groups, int64_t target) {
+    const int64_t kth = 8 * groups - target;
+    return kth >= 1 ? (unsigned long long)kth : 0ull;
+}
+
+// grid = (workgroups per segment, n_seg): workgroup x of segment y strides over that segment's groups.  As in k_select_hist the bins are
+// private to the workgroup in LDS and merged once, one atomic per non-empty bin and workgroup, into the segment's global bins.
+template <int PASS, bool SEG>
+__global__ __launch_bounds__(256) void k_select_hist_batch(const float4 *__restrict__ logit, int64_t m, const int64_t *__restrict__ edges,
+                                                           const int64_t *__restrict__ targets, const int32_t *__restrict__ seg,
+                                                           const unsigned *__restrict__ seg_max, const SelectState *__restrict__ st,
+                                                           unsigned *__restrict__ hist) {
+    __shared__ unsigned s_h[kSelBins];
+    const int s = blockIdx.y;
+    const int64_t p0 = edges[s], p1 = edges[s + 1];
+    if (p0 + (int64_t)blockIdx.x * 256 >= p1) return;                          // (uniform over the workgroup) nothing of this segment here
+    const unsigned long long rank = PASS ? st[s].rank : first_rank(p1 - p0, targets[s]);
+    if (rank == 0ull) return;
+    const unsigned prefix = PASS ? st[s].prefix : 0u;
+    for (int i = threadIdx.x; i < kSelBins; i += 256) s_h[i] = 0;
+    __syncthreads();
+    select_count<PASS, SEG>(s_h, logit, p0, p1, seg, seg_max, prefix);
+    __syncthreads();
+    unsigned *mine = hist + (size_t)s * kSelBins;
+    for (int i = threadIdx.x; i < kSelBins; i += 256)
+        if (s_h[i]) atomicAdd(&mine[i], s_h[i]);
+}
+
+// one workgroup per segment: k_select_pick on the segment's own bins and state
+template <int PASS>
+__global__ __launch_bounds__(256) void k_select_pick_batch(unsigned *__restrict__ hist_all, SelectState *__restrict__ st_all,
+                                                           const int64_t *__restrict__ edges, const int64_t *__restrict__ targets) {
+    __shared__ unsigned long long s_part[256];
+    const int s = blockIdx.x;
+    unsigned *hist = hist_all + (size_t)s * kSelBins;
+    SelectState *st = st_all + s;
+    const unsigned long long rank = PASS ? st->rank : first_rank(edges[s + 1] - edges[s], targets[s]);
+    const unsigned prefix = PASS ? st->prefix : 0u;
+    if (rank == 0ull) {                                                         // (uniform) no threshold: everything above -inf is kept
+        if (threadIdx.x == 0) { st->rank = 0ull; if (PASS == 2) st->thr = -__builtin_huge_valf(); }
+        return;
+    }
+    select_walk<PASS>(hist, st, rank, prefix, s_part);
+}
+
+// one thread per group over the whole batch; its segment by binary search of the edges (in LDS).  The edges cover [0, m) (0 first, m last,
+// rising: hipops.topk_keep_batch checks them on the host), so every group has a segment.
+template <bool SEG>
+__global__ __launch_bounds__(256) void k_keep_thr_batch(const float4 *__restrict__ logit, int64_t m, const int64_t *__restrict__ edges, int n_seg,
+                                                        const int32_t *__restrict__ seg, const unsigned *__restrict__ seg_max,
+                                                        const SelectState *__restrict__ st, uint8_t *__restrict__ keep) {
+    __shared__ int64_t s_e[kMaxSegments + 1];
+    for (int i = threadIdx.x; i <= n_seg; i += 256) s_e[i] = edges[i];
+    __syncthreads();
+    int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    int lo = 0, hi = n_seg;                                                      // the last s with s_e[s] <= p
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (s_e[mid] <= p) lo = mid; else hi = mid;
+    }
+    const float thr = st[lo].thr;
+    const float4 a = logit[2 * p], b = logit[2 * p + 1];
+    const float mx = SEG ? ord2f(seg_max[seg[p]]) : max8(a, b);
+    const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint64_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) bits |= (uint64_t)((v[k] > thr || v[k] == mx) ? 1 : 0) << (8 * k);
+    reinterpret_cast<uint64_t *>(keep)[p] = bits;
+}
+
+int64_t select_batch_ws_bytes(int n_seg) { return align_up((int64_t)sizeof(SelectState) * n_seg, 256) + (int64_t)4 * kSelBins * n_seg; }
+
+template <bool SEG>
+int select_and_keep_batch(const float *logit, int64_t m, const int64_t *edges, int n_seg, const int64_t *targets, const int32_t *seg,
+                          const unsigned *seg_max, uint8_t *keep_out, void *ws, hipStream_t s) {
+    SelectState *st = static_cast<SelectState *>(ws);
+    unsigned *hist = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + align_up((int64_t)sizeof(SelectState) * n_seg, 256));
+    FPCC_HIP(hipMemsetAsync(ws, 0, (size_t)select_batch_ws_bytes(n_seg), s));
+    const float4 *lg = reinterpret_cast<const float4 *>(logit);
+    // one workgroup per CU over all segments, the bound of the single call (see k_select_hist: the merges of a segment's workgroups land
+    // on a few hot bins); a segment that is larger than its share strides, one that is smaller leaves early
+    const unsigned per_seg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_for(m, 256), 256 / n_seg));
+    const dim3 grid(per_seg, (unsigned)n_seg);
+    hipLaunchKernelGGL((k_select_hist_batch<0, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL(k_select_pick_batch<0>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
+    hipLaunchKernelGGL((k_select_hist_batch<1, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL(k_select_pick_batch<1>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
+    hipLaunchKernelGGL((k_select_hist_batch<2, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL(k_select_pick_batch<2>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
+    hipLaunchKernelGGL(k_keep_thr_batch<SEG>, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, s, lg, m, edges, n_seg, seg, seg_max,
+                       (const SelectState *)st, keep_out);
+    return check_hip(hipGetLastError(), "topk select (batch)");
 }
 
 }  // namespace
@@ -270,4 +390,29 @@ extern "C" int64_t fpcc_topk_keep_cells(const float *logit, int64_t m, const int
                        seg_max);
     FPCC_LAUNCHED(k_seg_max);
     return select_and_keep<true>(logit, m, cell_of_group, (const unsigned *)seg_max, 8 * m - target, keep_out, ws, s);
+}
+
+extern "C" int64_t fpcc_topk_keep_batch(const float *logit, int64_t m, const int64_t *seg_edges, int n_seg, const int32_t *cell_of_group,
+                                        int64_t n_cells, const int64_t *targets, uint8_t *keep_out, void *ws, int64_t ws_bytes,
+                                        void *stream) {
+    if (m < 0 || n_cells < 0) return fail_arg("topk_keep_batch: negative size");
+    if (n_seg < 1 || n_seg > kMaxSegments) return fail_arg("topk_keep_batch: 1 <= n_seg <= 256 (FPCC_TOPK_BATCH_MAX_SEGMENTS)");
+    const int64_t select = select_batch_ws_bytes(n_seg);
+    const int64_t need = select + align_up(4 * (n_cells > 0 ? n_cells : 1), 256);
+    if (!ws) return need;
+    if (ws_bytes < need) { set_error("topk_keep_batch: workspace %lld < %lld", (long long)ws_bytes, (long long)need); return FPCC_E_WORKSPACE; }
+    if (m == 0) return FPCC_OK;
+    if (!logit || !keep_out || !seg_edges || !targets) return fail_arg("topk_keep_batch: null pointer");
+    if ((reinterpret_cast<uintptr_t>(logit) & 15) || (reinterpret_cast<uintptr_t>(keep_out) & 7) || (reinterpret_cast<uintptr_t>(ws) & 15) ||
+        (reinterpret_cast<uintptr_t>(seg_edges) & 7) || (reinterpret_cast<uintptr_t>(targets) & 7))
+        return fail_arg("topk_keep_batch: logit / workspace must be 16-byte, keep_out / seg_edges / targets 8-byte aligned");
+    hipStream_t s = as_stream(stream);
+    if (!cell_of_group)
+        return select_and_keep_batch<false>(logit, m, seg_edges, n_seg, targets, nullptr, nullptr, keep_out, ws, s);
+    unsigned *seg_max = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + select);
+    FPCC_HIP(hipMemsetAsync(seg_max, 0, (size_t)(4 * n_cells), s));       // 0 orders below every float
+    hipLaunchKernelGGL(k_seg_max, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, s, reinterpret_cast<const float4 *>(logit), m, cell_of_group,
+                       seg_max);
+    FPCC_LAUNCHED(k_seg_max);
+    return select_and_keep_batch<true>(logit, m, seg_edges, n_seg, targets, cell_of_group, (const unsigned *)seg_max, keep_out, ws, s);
 }

@@ -7,7 +7,7 @@ there is no alternative implementation: without the library or a GPU these funct
 import collections
 import ctypes as C
 import functools
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -85,6 +85,7 @@ _SIGS = {
     'fpcc_child_mask': (_i32, [_vp, _i64, _vp, _vp]),
     'fpcc_topk_keep': (_i64, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     'fpcc_topk_keep_cells': (_i64, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
+    'fpcc_topk_keep_batch': (_i64, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_gather_rows_f32': (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _i32, _vp]),
     'fpcc_compact_coords': (_i64, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_int_init': (_i32, []),
@@ -1130,6 +1131,48 @@ def topk_keep_cells(logit: torch.Tensor, cell_of_group: torch.Tensor, n_cells: i
     ws, need = _ws(lambda: L.fpcc_topk_keep_cells(None, m, None, n_cells, target, None, None, 0, None), logit.device)
     _ok(L.fpcc_topk_keep_cells(_dev(logit, torch.float32, 'logit'), m, _dev(cell_of_group, torch.int32, 'cell_of_group'),
                                n_cells, int(target), out.data_ptr(), ws.data_ptr(), need, _stream()))
+    return out
+
+
+TOPK_BATCH_MAX_SEGMENTS = 256       # FPCC_TOPK_BATCH_MAX_SEGMENTS of include/fpcc_hip.h
+
+
+def topk_keep_batch(logit: torch.Tensor, seg_edges: Sequence[int], targets: Sequence[int], cell_of_group: Optional[torch.Tensor] = None,
+                    n_cells: int = 0) -> torch.Tensor:
+    """uint8 [8 m]: topk_keep (cell_of_group None) / topk_keep_cells of every segment of a batch in ONE set of launches
+    (fpcc_topk_keep_batch).  seg_edges: host list [n_seg + 1] of GROUP offsets, 0 first and m last; targets: host list [n_seg];
+    cell_of_group: int32 [m] GLOBAL cell ids in [0, n_cells), a cell inside one segment.  keep[8 * a: 8 * b] of segment [a, b) equals,
+    byte for byte, what the single call gives on logit[8 * a: 8 * b] alone (with local cell ids).  More than TOPK_BATCH_MAX_SEGMENTS
+    segments: one single call per segment (the per-segment form of the same contract).  That fallback hands every call the GLOBAL cell
+    ids and n_cells, so each of its calls sizes and clears a cell workspace for the whole batch: correct, and there so that no batch
+    size is refused, not to be fast."""
+    n = logit.numel()
+    m = n // 8
+    edges, targets = [int(e) for e in seg_edges], [int(t) for t in targets]
+    n_seg = len(targets)
+    if n % 8 or (cell_of_group is not None and cell_of_group.shape[0] != m):
+        raise ValueError('logits in groups of 8 candidates, one cell id per group expected')
+    if n_seg < 1 or len(edges) != n_seg + 1 or edges[0] != 0 or edges[-1] != m or any(b < a for a, b in zip(edges[:-1], edges[1:])):
+        raise ValueError('seg_edges must rise from 0 to the number of groups, one more entry than targets')
+    for t, a, b in zip(targets, edges[:-1], edges[1:]):
+        if t < 0 or not 8 * (b - a) > t:
+            raise ValueError('fewer candidates than points to keep')
+    if n_seg > TOPK_BATCH_MAX_SEGMENTS:
+        keep = []
+        for t, a, b in zip(targets, edges[:-1], edges[1:]):
+            if cell_of_group is None:
+                keep.append(topk_keep(logit[8 * a: 8 * b], t))
+            else:
+                keep.append(topk_keep_cells(logit[8 * a: 8 * b], cell_of_group[a:b].contiguous(), n_cells, t))
+        return torch.cat(keep)
+    out = torch.empty(n, dtype=torch.uint8, device=logit.device)
+    L = lib()
+    ws, need = _ws(lambda: L.fpcc_topk_keep_batch(None, m, None, n_seg, None, n_cells, None, None, None, 0, None), logit.device)
+    # one small copy for both lists, from pinned memory: the host does not wait for the stream
+    meta = torch.tensor(edges + targets, dtype=torch.int64, pin_memory=True).to(logit.device, non_blocking=True)
+    _ok(L.fpcc_topk_keep_batch(_dev(logit, torch.float32, 'logit'), m, meta.data_ptr(), n_seg,
+                               _dev(cell_of_group, torch.int32, 'cell_of_group', True), int(n_cells), meta.data_ptr() + 8 * (n_seg + 1),
+                               out.data_ptr(), ws.data_ptr(), need, _stream()))
     return out
 
 

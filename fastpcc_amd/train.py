@@ -256,13 +256,18 @@ def ddp_bench(trainer: Trainer, data: Iterator[PCData], steps: int, warmup: int,
     return elapsed_max, total_voxels, comm_ms, last
 
 
+V2_MODELS = ('baseline_r1', 'baseline_r3', 'baseline_r5')
+
+
 def ddp_training_record(steps: int, warmup: int, device: torch.device, resolution: int = 128,
-                        cfg: Optional[TrainConfig] = None) -> Optional[dict]:
+                        cfg: Optional[TrainConfig] = None, model_name: str = 'baseline_r1') -> Optional[dict]:
     """cfg#5 on the ranks of the EXISTING process group (bench.py --gpus N calls this after its replica timing, so the
     driver's own scaling command produces the DDP figure too): lossy_coord_v2/baseline_r1, global batch 8 split 8 / N per
     rank, gradients all-reduced over RCCL by DDP.  Collective; rank 0 returns the record, other ranks None."""
     from .codecs.lossy_coord_v2 import Model
-    from .codecs.lossy_coord_v2.model_config import baseline_r1
+    from .codecs.lossy_coord_v2 import model_config
+    if model_name not in V2_MODELS:
+        raise ValueError(f'model must be one of {V2_MODELS}')
     cfg = cfg or TrainConfig()
     rank, world, _ = replicas.env_rank()
     if cfg.batch_size % world:
@@ -274,7 +279,7 @@ def ddp_training_record(steps: int, warmup: int, device: torch.device, resolutio
     model = data = None
     try:
         torch.manual_seed(0)                              # same initial weights on every rank
-        model = Model(baseline_r1()).to(device).train()
+        model = Model(getattr(model_config, model_name)()).to(device).train()
         data = synthetic_batches(rank, world, cfg, device, resolution)
         probe = next(data)
         probe.training_step = 0
@@ -293,7 +298,7 @@ def ddp_training_record(steps: int, warmup: int, device: torch.device, resolutio
     if rank != 0:
         return None
     n_param = sum(p.numel() for p in unwrap(trainer.model).parameters())
-    return {'workload': f'lossy_coord_v2/baseline_r1 optimisation step, global batch {cfg.batch_size} ShapeNet-like clouds at '
+    return {'workload': f'lossy_coord_v2/{model_name} optimisation step, global batch {cfg.batch_size} ShapeNet-like clouds at '
                         f'{resolution}^3 (cfg#5), {cfg.batch_size // world} per rank, forward + backward + all-reduce + AdamW',
             'ranks': world, 'parallelism': f'ddp{world}', 'ms_per_step': round(elapsed_max / steps * 1e3, 2),
             'clouds_per_s': round(cfg.batch_size * steps / elapsed_max, 3), 'voxels_per_step': round(total_voxels / steps),
@@ -302,9 +307,10 @@ def ddp_training_record(steps: int, warmup: int, device: torch.device, resolutio
             'last_loss': None if last is None else round(last['loss'], 2)}
 
 
-def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Optional[TrainConfig] = None) -> Optional[dict]:
-    """times `steps` optimisation steps of lossy_coord_v2/baseline_r1 on synthetic ShapeNet-like batches; rank 0 returns
-    the result record, other ranks None"""
+def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Optional[TrainConfig] = None,
+          model_name: str = 'baseline_r1') -> Optional[dict]:
+    """times `steps` optimisation steps of lossy_coord_v2/<model_name> (baseline_r1 | r3 | r5) on synthetic ShapeNet-like batches;
+    rank 0 returns the result record, other ranks None"""
     cfg = cfg or TrainConfig()
     rank, world, local = replicas.env_rank()
     if world != gpus:
@@ -313,16 +319,16 @@ def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Option
     device = torch.device('cuda', local)
     replicas.bind_to_device_numa_node(local)
     replicas.init('nccl')
-    rec = ddp_training_record(steps, warmup, device, resolution, cfg)
+    rec = ddp_training_record(steps, warmup, device, resolution, cfg, model_name)
     if rank != 0:
         return None
     if 'skipped' in rec:
         raise SystemExit(rec['skipped'])
-    return {'metric': 'training clouds/sec, lossy_coord_v2 baseline_r1 (DDP)', 'value': rec['clouds_per_s'],
+    return {'metric': f'training clouds/sec, lossy_coord_v2 {model_name} (DDP)', 'value': rec['clouds_per_s'],
             'unit': 'clouds/s', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
             'ms_per_step': rec['ms_per_step'], 'higher_is_better': True, 'scaling': 'strong',
             'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': f'lossy_coord_v2/baseline_r1 training, global batch {cfg.batch_size} ShapeNet-like clouds at '
+            'config': {'workload': f'lossy_coord_v2/{model_name} training, global batch {cfg.batch_size} ShapeNet-like clouds at '
                                    f'{resolution}^3 (cfg#5), {cfg.batch_size // world} per rank',
                        'parallelism': f'ddp{world}', 'voxels_per_step': rec['voxels_per_step'],
                        'parameters': rec['parameters'], 'gradient_bytes': rec['gradient_bytes'],

@@ -442,6 +442,22 @@ int64_t fpcc_compact_coords(const int64_t *pkeys, int64_t m, const uint8_t *mask
 int64_t fpcc_topk_keep_cells(const float *logit, int64_t m, const int32_t *cell_of_group, int64_t n_cells, int64_t target,
                              uint8_t *keep_out, void *ws, int64_t ws_bytes, void *stream);
 
+/* The two calls above for MANY segments (the clouds of a batch: training, compress_many / decompress_many) in one set of launches.
+ * Segment s holds the candidate GROUPS [seg_edges[s], seg_edges[s+1]) (device int64 [n_seg + 1], seg_edges[0] = 0, the last = m) and is
+ * pruned to targets[s] (device int64 [n_seg]) candidates.  Contract: keep_out[8 * seg_edges[s] : 8 * seg_edges[s+1]] is byte for byte
+ * what fpcc_topk_keep (cell_of_group == NULL: a cell is the group itself) or fpcc_topk_keep_cells writes for that segment alone
+ * with target targets[s]: only the threshold -- the (8 * groups - target)-th smallest of the segment's candidates, cell maxima
+ * ranked as +inf -- is a segment's own.  Cell ids are global ([0, n_cells) over the whole batch) and a cell lies inside one segment
+ * (rows of the coarsest decoder level are batch-major), so the local-maximum rule needs no segment knowledge.
+ * The number of launches does not depend on n_seg (the histogram passes take the segment as their second grid dimension, the bins
+ * are [n_seg][2048]); nothing is read back.  1 <= n_seg <= FPCC_TOPK_BATCH_MAX_SEGMENTS, otherwise FPCC_E_ARG (callers fall
+ * back to one call per segment).  A target that is not below a segment's candidate count keeps every candidate above -inf, as in
+ * the single calls.  The edges are device memory and are NOT checked here: the caller guarantees 0 first, m last and a monotone rise
+ * (hipops.topk_keep_batch checks its host lists before the copy).  ws (16-byte aligned): the size the call returns with ws == NULL. */
+#define FPCC_TOPK_BATCH_MAX_SEGMENTS 256
+int64_t fpcc_topk_keep_batch(const float *logit, int64_t m, const int64_t *seg_edges, int n_seg, const int32_t *cell_of_group,
+                             int64_t n_cells, const int64_t *targets, uint8_t *keep_out, void *ws, int64_t ws_bytes, void *stream);
+
 /* Rate term of the noisy deep-factorised bottleneck (training): for y [n][c] (row stride ldy) and the per-channel parameters of a
  * 1-3-3-3-3-1 logit network -- weights[i] [c][f_out][f_in], biases[i] [c][f_out], factors[i] [c][f_out], raw as stored
  * (softplus / tanh applied inside) --
