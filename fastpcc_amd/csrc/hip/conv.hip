@@ -22,13 +22,18 @@
 // Multi-offset layers with 32-multiple channel counts are evaluated GROUPED (summation order 3 -- part of the stream format, see
 // FPCC_NUMERICS_VERSION): the kernel offsets form four fixed groups, one wave of a workgroup each, partial sums added in group
 // order -- by four waves of a workgroup that meet in LDS (k_conv_wave<..., OG = 4>: maps below 100 K rows, which need the
-// parallelism) or by one wave that folds its accumulator into a running sum at every group boundary (k_conv_wave<..., FOLD>: large
-// maps); both leave the same bits.
+// parallelism) or by one wave that folds its accumulator into a running sum at every group boundary: k_conv_wave<..., FOLD>
+// (32-row units, three waves per SIMD) from 100 K rows, and k_conv_fold64 (64 x 64 units in which every A and B fragment feeds two
+// MFMAs, running sums in registers, two waves per SIMD) from 200 K rows on maps with a row order and 64 | 128 output channels.
+// All three leave the same bits.
 //
 // Roofline: 2 * pairs * C_in * C_out algorithmic flop against the fp32 MFMA peak.  Measured limits of this design are in
 // profiles/r02/wave_kernel_sweeps.md and profiles/r03/{sq_counters,grouped_occupancy,grouped_fold,clock_ramp}.md: each VMEM
 // instruction costs ~30 SIMD cycles of issue that more waves do not hide, the B stream (256 B per MFMA from L2) caps the wave
 // kernel at ~100 TFLOP/s on the 272 K-row maps at 2.4 GHz, and inside a codec step the power management grants ~2.16 GHz.
+// The folded 32 x 64 unit issues 12 VMEM instructions per 32 MFMAs (384 B of operands per MFMA), the 64 x 64 unit 16 per 64
+// (256 B).  On the bench's 286 K .. 4.36 M-row maps the 64-row unit executes 2.2-2.6 % more pairs and the 27-offset launches take
+// about 3 % less time in all (per shape 2-6 % less; single launches between 6 % less and 2 % more): profiles/r07/fold64.md.
 #include "conv_common.h"
 #include <atomic>
 #include <cstdlib>
@@ -862,6 +867,228 @@ __global__ __launch_bounds__(256, 3) void k_conv_wave22(ConvArgs a, const float 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Folded 64 x 64 wave unit: k_conv_wave22's operand path (every A and B fragment feeds two MFMAs: 16 vector-memory instructions per 64
+// MFMAs against 12 per 32 in the folded 32 x 64 unit) with the FOLD rule of k_conv_wave -- summation order 3 on ONE wave.  Four
+// accumulators and four running sums stay in registers (128 of the 256 a lane has at two waves per SIMD; operands 64, addresses ~25).
+//
+// The fold boundaries are those of the UNIT's offset mask (the union over its two 32-row blocks), not of each block's own.  That
+// leaves the bits of the 32-row folded kernel, block by block:
+//   * an offset only the other block has: this block's rows read the zero row, every term is fma(0, w, acc) == acc -- the case a
+//     single absent row inside a present block already is (acc is never -0: it restarts as +0, and (+-0) + (+0) == +0);
+//   * a group of which only the other block has offsets: this block's accumulator takes only such terms from its restart value +0,
+//     stays +0, and the unit folds t = t + (+0) (t = +0 for the first group) -- exactly fold_zero of the 32-row kernel;
+//   * a group neither block has: fold_zero for both, as in the 32-row kernel.
+// So per block and group the running sum receives either the block's own order-1 partial sum or +0, in group order.
+// The price: a unit executes every offset either of its blocks has (pattern row order puts like blocks side by side), and a launch
+// has half as many units -- for large maps with a row order (launch_grouped).
+__global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_units) {
+    constexpr int CH = 32, G8 = 4;
+    constexpr int SB = 0x6;                         // the next stage's address arithmetic may float between the MFMAs (k_conv_wave)
+    __shared__ int32_t s_nbr_all[4][kMaxOffsets * 64];
+
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: see k_conv_wave)
+    const int li = lane & 31, lh = lane >> 5;
+    const unsigned n_cg = (unsigned)(nbt / 2);
+    const unsigned blk = a.row_order ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
+    const unsigned unit = blk * 4u + (unsigned)wv;
+    if (unit >= n_units) return;                    // no barrier below: a wave may leave on its own
+    const unsigned rb_ = unit / n_cg, cg = unit - rb_ * n_cg;
+    const int64_t row0 = (int64_t)rb_ * 64;
+    const int c_in = a.c1 + a.c2;
+    const int n_chunks = c_in / CH;
+    const int n_off = a.n_off;
+    int32_t *s_nbr = s_nbr_all[wv];
+
+    // lane = position `lane` of the unit's 64 rows here; in the MFMA phase lane (i, h) serves rows i and 32 + i
+    int32_t my_row = -1;
+    if (row0 + lane < a.n_out) my_row = a.row_order ? a.row_order[row0 + lane] : (int32_t)(row0 + lane);
+    unsigned wmask = 0;
+    if (table_is_row_major(a)) {
+        // the row's entries as 16-byte pieces of its line (by position beside a row order: conv_common.h); no load depends on another
+        const int64_t p = row0 + lane < a.n_out ? row0 + lane : a.n_out - 1;     // past the end: re-read the last row, marked absent below
+        const i32x4 *rowp = reinterpret_cast<const i32x4 *>(a.nbr + p * a.nbr_os);
+        const int last_piece = (n_off - 1) >> 2;
+        i32x4 q[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) q[j] = rowp[min(j, last_piece)];
+#pragma unroll
+        for (int j = 0; j < 7; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int k = 4 * j + e;
+                if (k >= kMaxOffsets) continue;
+                const int32_t v = (k < n_off && my_row >= 0) ? q[j][e] : -1;
+                if (k < n_off) s_nbr[k * 64 + lane] = v;
+                if (__ballot(v >= 0) != 0ull) wmask |= 1u << k;
+            }
+    } else {
+        for (int k = 0; k < n_off; ++k) {
+            int32_t v = -1;
+            if (my_row >= 0) v = a.nbr[(int64_t)k * a.nbr_ks + (int64_t)my_row * a.nbr_os];
+            s_nbr[k * 64 + lane] = v;
+            if (__ballot(v >= 0) != 0ull) wmask |= 1u << k;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    wmask = __builtin_amdgcn_readfirstlane(wmask);
+
+    f32x16 acc[2][2], tsum[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[rb][nb][r] = 0.0f;
+
+    // running sum over the offset groups finished so far (n_folded of them): fold_acc / fold_zero of k_conv_wave, for four accumulators
+    int n_folded = 0, cur_g = 0;
+    auto fold_acc = [&]() {
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    tsum[rb][nb][r] = n_folded ? tsum[rb][nb][r] + acc[rb][nb][r] : acc[rb][nb][r];
+                    acc[rb][nb][r] = 0.0f;
+                }
+        ++n_folded;
+    };
+    auto fold_zero = [&]() {                              // a group none of whose offsets the unit has: its partial sum is +0
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tsum[rb][nb][r] = n_folded ? tsum[rb][nb][r] + 0.0f : 0.0f;
+        ++n_folded;
+    };
+    unsigned rest_c = wmask;
+    int cc_c = 0;
+    if (wmask) {
+        cur_g = offset_group_of(__ffs(wmask) - 1, n_off);
+        for (int gz = 0; gz < cur_g; ++gz) fold_zero();
+    }
+
+    const int n_stages = __popc(wmask) * n_chunks;
+    if (n_stages > 0) {
+        const int64_t chunk_floats = (int64_t)G8 * nbt * 256;
+        const float *wp_g = wp + ((int64_t)cg * 2) * 256 + lane * 4;
+        const float *const zero = (const float *)g_zero_row + 4 * lh;
+        const float *const x1b = a.x1 + 4 * lh, *const x2b = a.x2 ? a.x2 + 4 * lh : zero;
+        const int64_t ld1 = a.ld1, ld2 = a.ld2;
+        const int n1 = a.c1 / CH;
+        const float *a1[2], *a2[2], *bpk;
+        int step[2];
+        auto set_offset = [&](int k) {
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+                const int32_t idx = s_nbr[k * 64 + 32 * rb + li];
+                const int32_t neg = idx >> 31;
+                const uint64_t m = (uint64_t)(int64_t)neg, z = reinterpret_cast<uint64_t>(zero) & m;
+                const int64_t row = idx & ~neg;
+                a1[rb] = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x1b + row * ld1) & ~m) | z);
+                a2[rb] = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x2b + row * ld2) & ~m) | z);
+                step[rb] = CH & ~neg;
+            }
+            bpk = wp_g + (int64_t)k * n_chunks * chunk_floats;
+        };
+        unsigned rest = wmask;
+        int cc_f = 0;
+        set_offset(__ffs(rest) - 1);
+        const float *ap[2], *bp;
+        auto next_stage = [&]() {
+            const bool in1 = cc_f < n1;                           // wave-uniform
+            const int c = in1 ? cc_f : cc_f - n1;
+            ap[0] = (in1 ? a1[0] : a2[0]) + c * step[0];
+            ap[1] = (in1 ? a1[1] : a2[1]) + c * step[1];
+            bp = bpk + cc_f * chunk_floats;
+            if (cc_f + 1 < n_chunks) {
+                ++cc_f;
+            } else {
+                const unsigned r2 = rest & (rest - 1);
+                if (r2) { rest = r2; cc_f = 0; set_offset(__ffs(r2) - 1); }
+            }
+        };
+        f32x4 ra[2][G8], rbv[G8][2];
+        next_stage();
+#pragma unroll
+        for (int g8 = 0; g8 < G8; ++g8) {
+            __builtin_amdgcn_sched_barrier(0);
+            ra[0][g8] = *reinterpret_cast<const f32x4 *>(ap[0] + 8 * g8);
+            __builtin_amdgcn_sched_barrier(0);
+            ra[1][g8] = *reinterpret_cast<const f32x4 *>(ap[1] + 8 * g8);
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+                __builtin_amdgcn_sched_barrier(0);
+                rbv[g8][nb] = *reinterpret_cast<const f32x4 *>(bp + ((int64_t)g8 * nbt + nb) * 256);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        for (int s = 0; s < n_stages; ++s) {
+            // compute position (one stage behind the fetch position): entering the first chunk of an offset of a later group
+            if (cc_c == 0) {
+                const int gk = offset_group_of(__ffs(rest_c) - 1, n_off);
+                if (gk != cur_g) {
+                    fold_acc();
+                    for (int gz = cur_g + 1; gz < gk; ++gz) fold_zero();
+                    cur_g = gk;
+                }
+            }
+            if (++cc_c == n_chunks) { cc_c = 0; rest_c &= rest_c - 1; }
+            next_stage();                                       // stage s + 1
+            __builtin_amdgcn_sched_barrier(SB);
+#pragma unroll
+            for (int g8 = 0; g8 < G8; ++g8) {
+                const f32x4 av0 = ra[0][g8], av1 = ra[1][g8];
+                const f32x4 b0 = rbv[g8][0], b1 = rbv[g8][1];
+#define FPCC_STEP(c)                                                                                     \
+                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0.c, b0.c, acc[0][0], 0, 0, 0);       \
+                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0.c, b1.c, acc[0][1], 0, 0, 0);       \
+                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1.c, b0.c, acc[1][0], 0, 0, 0);       \
+                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1.c, b1.c, acc[1][1], 0, 0, 0);
+                FPCC_STEP(x) FPCC_STEP(y) FPCC_STEP(z) FPCC_STEP(w)
+#undef FPCC_STEP
+                __builtin_amdgcn_sched_barrier(SB);
+                ra[0][g8] = *reinterpret_cast<const f32x4 *>(ap[0] + 8 * g8);
+                __builtin_amdgcn_sched_barrier(SB);
+                ra[1][g8] = *reinterpret_cast<const f32x4 *>(ap[1] + 8 * g8);
+#pragma unroll
+                for (int nb = 0; nb < 2; ++nb) {
+                    __builtin_amdgcn_sched_barrier(SB);
+                    rbv[g8][nb] = *reinterpret_cast<const f32x4 *>(bp + ((int64_t)g8 * nbt + nb) * 256);
+                }
+                __builtin_amdgcn_sched_barrier(SB);
+            }
+        }
+    }
+    if (wmask) { fold_acc(); ++cur_g; }
+    for (int gz = cur_g; gz < 4; ++gz) fold_zero();
+
+    const float slope = (a.act == FPCC_ACT_PRELU && a.slope) ? a.slope[0] : 0.0f;
+    float bias2[2];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) bias2[nb] = a.bias ? a.bias[32 * ((int)cg * 2 + nb) + li] : 0.0f;
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+        int64_t dsts[16];
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int64_t o = __shfl(my_row, 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh);
+            dsts[reg] = o < 0 ? -1 : o;             // grouped shapes: one group, no output map
+        }
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int64_t dst = dsts[reg];
+            if (dst < 0) continue;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb)
+                a.out[dst * a.ldo + 32 * ((int)cg * 2 + nb) + li] = finish(tsum[rb][nb][reg], bias2[nb], a.act, slope, a.clip);
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void k_pack_weights(const float *__restrict__ w, int64_t n_mats, int c_in, int c_out,
                                                       float *__restrict__ wp) {
     // one thread per packed element: [m][cc][g8][nb][h][i][j] <- w[m][32 cc + 8 g8 + 4 h + j][32 nb + i]
@@ -907,15 +1134,15 @@ int launch_mfma_cfg(ConvArgs a, hipStream_t s) {
 // which is therefore refused unless the process runs with FPCC_EXPERIMENT=1 and has no environment variable.
 // kKnobStamps (0 | 16: the stamped builds of the grouped and the LDS-operand kernel, same bits) has no environment variable either.
 enum { kKnobWaveOn = 0, kKnobWaveNbw = 1, kKnobWaveSb = 2, kKnobStamps = 3, kKnobGroupedFoldRows = 4, kKnobMfmaCfg = 5, kKnobPointwiseRows = 6,
-       kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobCount = 13 };
-int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+       kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobFold64 = 13, kKnobCount = 14 };
+int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 int knob(int k) {
     if (g_knob[k] < 0) {
         static const char *names[kKnobCount] = {"FPCC_CONV_WAVE", "FPCC_WAVE_NBW", "FPCC_WAVE_SB", "", "FPCC_GROUPED_FOLD_ROWS",
                                                 "FPCC_MFMA_TILE", "FPCC_POINTWISE_MIN_ROWS", "", "FPCC_GROUPED_NBW",
                                                 "FPCC_WAVE22_MIN_ROWS", "FPCC_LDS_MIN_ROWS", "FPCC_LDS_ROW_BLOCKS",
-                                                "FPCC_CONV_PERSIST"};
-        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0};
+                                                "FPCC_CONV_PERSIST", "FPCC_CONV_FOLD64"};
+        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0, 0};
         const char *e = names[k][0] ? getenv(names[k]) : nullptr;
         g_knob[k] = e ? atoi(e) : defaults[k];
     }
@@ -1057,6 +1284,29 @@ int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s
     return check_hip(hipGetLastError(), "k_conv_wave(folded)");
 }
 
+// Folded 64 x 64 wave units (k_conv_fold64) for the folded launches of the shapes they were measured on -- 27 offsets, 64 | 128
+// output channels: knob 13 / FPCC_CONV_FOLD64 = 0: on maps with a row order (pattern order puts like blocks side by side) of at
+// least kFold64Rows rows, 1: never (the 32-row folded units), 2: on every folded launch of such a shape.  Every other shape, maps
+// without a row order and the persistent folded form (knob 12) keep the 32-row units.
+// Threshold from the bench's own maps (profiles/r07/fold64.md): 286 K, 1.13 M and 4.36 M rows gain at both widths; there is no
+// measurement between 100 K and 200 K rows, which keep the 32-row units.
+constexpr int64_t kFold64Rows = 200 * 1024;
+std::atomic<long long> g_fold64_launches{0};       // fpcc_conv_fold64_launches(): which unit a launch took (tests)
+inline bool use_fold64(const ConvArgs &a, int nbt) {
+    if ((nbt != 2 && nbt != 4) || a.n_off != kMaxOffsets || knob(kKnobPersist) > 0) return false;
+    const int v = knob(kKnobFold64);
+    if (v) return v >= 2;
+    return a.row_order && a.n_out >= kFold64Rows;
+}
+
+int launch_fold64(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
+    const int64_t units = ((a.n_out + 63) / 64) * (nbt / 2);
+    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
+    hipLaunchKernelGGL(k_conv_fold64, dim3((unsigned)((units + 3) / 4), 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    g_fold64_launches.fetch_add(1, std::memory_order_relaxed);
+    return check_hip(hipGetLastError(), "k_conv_fold64");
+}
+
 int launch_grouped(const ConvArgs &a, const float *wp, hipStream_t s) {
     const int nbt = a.c_out / 32;
     // both operands through LDS (conv_lds.hip) on maps of at least FPCC_LDS_MIN_ROWS rows (knob 10; 0 = never); same order 3
@@ -1066,8 +1316,10 @@ int launch_grouped(const ConvArgs &a, const float *wp, hipStream_t s) {
         if (rc != -1) return rc;
     }
     const int64_t fold_rows = knob(kKnobGroupedFoldRows);
-    if (fold_rows > 0 && a.n_out >= fold_rows && knob(kKnobGroupedNbw) <= 0)
+    if (fold_rows > 0 && a.n_out >= fold_rows && knob(kKnobGroupedNbw) <= 0) {
+        if (use_fold64(a, nbt)) return launch_fold64(a, wp, nbt, s);
         return nbt % 2 == 0 ? launch_folded_cfg<2>(a, wp, nbt, s) : launch_folded_cfg<1>(a, wp, nbt, s);
+    }
     int nbw = knob(kKnobGroupedNbw);
     if (nbw <= 0) nbw = a.n_out >= 40 * 1024 ? 2 : 1;        // measured: 64 columns per workgroup from ~40 K rows (profiles/r03/grouped_probe.md)
     while (nbw > nbt || nbt % nbw) nbw >>= 1;
@@ -1403,6 +1655,8 @@ extern "C" int fpcc_conv_debug_stamps(unsigned long long *buf, int64_t n_u64) {
     FPCC_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_cap), &cap, sizeof(cap)));
     return set_lds_stamp_buffer(buf, cap);
 }
+
+extern "C" long long fpcc_conv_fold64_launches(void) { return g_fold64_launches.load(std::memory_order_relaxed); }
 
 extern "C" int fpcc_conv_set_tuning(int which, int value) {
     if (which < 0 || which >= kKnobCount) return fail_arg("conv_set_tuning: unknown knob");

@@ -42,6 +42,7 @@ _SIGS = {
     'fpcc_conv_f32_pk': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _i32, _i32,
                                 _vp, _i64, _i64, _vp, _i32, _i64, _i32, _vp, _f32, _vp, _vp, _i64, _vp]),
     'fpcc_conv_set_tuning': (_i32, [_i32, _i32]),
+    'fpcc_conv_fold64_launches': (_i64, []),
     'fpcc_conv_debug_stamps': (_i32, [_vp, _i64]),
     'fpcc_conv_i8_debug_stamps': (_i32, [_vp, _i64]),
     'fpcc_time_next_launch': (_i32, [_vp, _vp]),
@@ -506,7 +507,13 @@ KNOB_WAVE_ON, KNOB_WAVE_NBW, KNOB_WAVE_SB, KNOB_WAVE_DBG, KNOB_MFMA_TILE, KNOB_P
 KNOB_GROUPED_FOLD_ROWS = 4       # rows from which grouped (order 3) layers run folded on one wave per unit; 0 = never
 KNOB_GROUPED_OFF, KNOB_GROUPED_NBW, KNOB_WAVE22_ROWS = 7, 8, 9      # 7: experiments only (FPCC_EXPERIMENT=1), changes the summation order
 KNOB_PERSIST = 12     # workgroups per CU of the persistent grouped / folded kernels (0 = off)
-KNOB_LDS_ROWS, KNOB_LDS_ROW_BLOCKS = 10, 11   # rows from which order-3 layers take both operands through LDS (0 = never); row blocks per workgroup (2 | 3 | 4)
+KNOB_FOLD64 = 13      # folded launches on 64 x 64 wave units: 0 = large maps with a row order, 1 = never, 2 = every folded launch
+KNOB_LDS_ROWS, KNOB_LDS_ROW_BLOCKS = 10, 11  # rows from which order-3 layers take both operands through LDS (0 = never); row blocks per workgroup (2 | 3 | 4)
+
+
+def conv_fold64_launches() -> int:
+    """launches of the folded 64 x 64 wave unit (k_conv_fold64) by this process so far"""
+    return int(lib().fpcc_conv_fold64_launches())
 
 
 def numerics_version() -> int:

@@ -229,8 +229,13 @@ int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int gr
  *      profiles/r04/persistent.md;
  *      values above 16 = that many workgroups in all)
  *   4  rows from which the grouped evaluation runs FOLDED -- one wave per unit adds up the four offset groups itself -- instead of on
- *      four waves per unit (FPCC_GROUPED_FOLD_ROWS, default 102400; 0 = never).  Same order 3, same bits. */
+ *      four waves per unit (FPCC_GROUPED_FOLD_ROWS, default 102400; 0 = never).  Same order 3, same bits.
+ *  13  unit of the folded launches of 27-offset layers with 64 | 128 output channels (FPCC_CONV_FOLD64): 0 = 64 x 64 wave units
+ *      (k_conv_fold64) on maps with a row order of at least 204800 rows, 32-row units elsewhere; 1 = 32-row units always; 2 = 64 x 64
+ *      units on every such launch.  The persistent form (knob 12) keeps its 32-row units.  Same order 3, same bits. */
 int fpcc_conv_set_tuning(int which, int value);
+/* Diagnostics: launches of k_conv_fold64 by this process so far (tests check which unit a forced launch took). */
+long long fpcc_conv_fold64_launches(void);
 /* Diagnostics (profiles/r04/small_level_stage.md): with knob 3 set to 16 every wave of the grouped kernel leaves 48 64-bit words in
  * `buf` (device memory, n_u64 words; NULL / 0 detaches): s_memtime at kernel entry [0], after the neighbour-table read [1], after the
  * first operands were requested [2], at the top of stage s [3 + min(s, 36)], after the last stage [40], after the partial-sum
