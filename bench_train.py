@@ -23,9 +23,11 @@ def main():
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--resolution', type=int, default=128)
     ap.add_argument('--model', choices=('baseline_r1', 'baseline_r3', 'baseline_r5'), default='baseline_r1')
+    ap.add_argument('--amp-dtype', choices=('', 'bfloat16'), default='',
+                    help="operand dtype of the training convolutions (train.amp_dtype): '' = fp32, bfloat16 = bf16 MFMA, fp32 accumulation")
     args = ap.parse_args()
     from fastpcc_amd.train import bench
-    out = bench(args.steps, args.warmup, args.gpus, args.resolution, model_name=args.model)
+    out = bench(args.steps, args.warmup, args.gpus, args.resolution, model_name=args.model, amp_dtype=args.amp_dtype)
     if out is not None:
         print(json.dumps(out))
     import torch.distributed as dist

@@ -13,7 +13,15 @@ MinkowskiEngine provides this through its own autograd functions; the model code
                      per-point linear      : W' = W^T
               dW = fpcc_conv_wgrad_f32(x, dy) on the forward's row maps
 so the backward pass runs on the same MFMA kernel as inference (plus the weight-gradient kernel).
+
+Mixed precision (`conv_autocast(torch.bfloat16)`): the same three products with bfloat16 operands on the bf16 MFMA
+(fpcc_conv_bf16 / fpcc_conv_wgrad_bf16), fp32 accumulation, fp32 results.  The forward casts x once and saves the bf16 copy, which
+the weight gradient reuses; the backward casts dy once for both gradient products; weights are packed from the fp32 parameters per
+call.  The choice is made by the forward and travels with the saved tensors -- autograd runs the backward on its own thread, where
+the thread-local context is not set.  Shapes outside fpcc_conv_bf16_supported, and kind 'tab', keep the fp32 code as it is.
 """
+import contextlib
+import threading
 from typing import Optional
 
 import torch
@@ -36,6 +44,124 @@ class ConvSpec:
 # 57.8 / 58.9 ms on the workgroup-tiled kernel -- no gain, the step is bound by the weight-gradient kernels and launch count; off.
 import os as _os
 PACK = 'fresh' if _os.environ.get('FPCC_TRAIN_PACK', 'off') in ('fresh', '1') else False
+
+
+_amp = threading.local()
+
+
+def compute_dtype() -> Optional[torch.dtype]:
+    """operand dtype of the training convolutions on the calling thread: None (fp32, today's path) | torch.bfloat16"""
+    return getattr(_amp, 'dtype', None)
+
+
+@contextlib.contextmanager
+def conv_autocast(dtype: Optional[torch.dtype]):
+    """inside the context the autograd convolutions of the CALLING thread take bfloat16 operands where the kernels support the shape
+    (dtype torch.bfloat16) or run as ever (None | torch.float32); nests, and restores the previous dtype on exit.  Outputs, gradients,
+    parameters and optimiser state stay fp32; everything reached with gradients disabled (inference, compress / decompress) ignores it"""
+    if dtype is torch.float32:
+        dtype = None
+    if dtype is not None and dtype is not torch.bfloat16:
+        raise ValueError(f'conv_autocast: only torch.bfloat16 (or None / torch.float32) is provided, got {dtype}')
+    prev = compute_dtype()
+    _amp.dtype = dtype
+    try:
+        yield
+    finally:
+        _amp.dtype = prev
+
+
+_KIND_SHAPE = {'k1': (1, 1), 'k3': (27, 1), 'k2s2': (8, 1), 'k2s2T': (1, 8), 'gen': (1, 8)}      # kind -> (n_offsets, groups) of the forward
+
+
+def _bf16_forward_ok(c_in: int, c_out: int, kind: str) -> bool:
+    """the calling thread asked for bfloat16 and the forward (hence the weight gradient) of this layer has a bf16 kernel"""
+    if compute_dtype() is not torch.bfloat16 or kind not in _KIND_SHAPE:
+        return False
+    return ops.conv_bf16_supported(c_in, c_out, *_KIND_SHAPE[kind])
+
+
+def _bf16_input_grad_ok(c_in: int, c_out: int, kind: str) -> bool:
+    """the input gradient of the layer (a convolution c_out -> c_in on the mirrored maps, 128 columns per launch) has a bf16 kernel"""
+    if c_in > 128 and c_in % 128:
+        return False
+    width = min(c_in, 128)
+    if kind == 'gen':                     # one packed GEMM [m, 8 c_out] @ [8 c_out, c_in]
+        return c_out % 16 == 0 and ops.conv_bf16_supported(8 * c_out, width, 1, 1)
+    n_offsets, groups = {'k1': (1, 1), 'k3': (27, 1), 'k2s2': (1, 8), 'k2s2T': (8, 1)}[kind]
+    return ops.conv_bf16_supported(c_out, width, n_offsets, groups)
+
+
+def _forward_bf16(x: torch.Tensor, w: torch.Tensor, s: ConvSpec, **epilogue) -> torch.Tensor:
+    """_forward (and the fused node's forward) on a bfloat16 x; the weights are packed from the fp32 parameter for this call"""
+    c_in, c_out = w.shape[-2], w.shape[-1]
+    n_offsets, groups = _KIND_SHAPE[s.kind]
+    wp = ops.pack_weights_bf16(w, n_offsets * groups, c_in, c_out)
+    if s.kind == 'k1':
+        return ops.conv_bf16(x, wp, c_out, s.n_in, **epilogue)
+    if s.kind == 'k3':
+        return ops.conv_bf16(x, wp, c_out, s.n_in, nbr=s.table, n_offsets=27, nbr_ks=s.n_in, nbr_os=1, row_order=s.row_order, **epilogue)
+    if s.kind == 'k2s2':
+        return ops.conv_bf16(x, wp, c_out, s.n_out, nbr=s.table, n_offsets=8, nbr_ks=1, nbr_os=8, **epilogue)
+    if s.kind == 'k2s2T':
+        return ops.conv_bf16(x, wp, c_out, s.n_in, groups=8, out_map=s.table, om_os=8, om_gs=1, out_rows=s.n_out, **epilogue)
+    return ops.conv_bf16(x, wp, c_out, s.n_in, groups=8, **epilogue)                                     # 'gen'
+
+
+def _wide_bf16(call, pack, width: int, rows: int, device) -> torch.Tensor:
+    """_wide for the bf16 kernels: `pack(lo, cols)` packs columns lo .. lo + cols of the gradient weights straight from the parameter"""
+    if width <= 128:
+        return call(pack(0, width), width, None)
+    out = torch.empty((rows, width), dtype=torch.float32, device=device)
+    for lo in range(0, width, 128):
+        call(pack(lo, 128), 128, out[:, lo: lo + 128])
+    return out
+
+
+def _input_grad_bf16(dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
+    """_input_grad on a bfloat16 dy: the mirrored convolution with W'[k] = W[mirror(k)]^T packed straight from W"""
+    c_in, c_out = w.shape[-2], w.shape[-1]
+    if s.kind == 'k1':
+        return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, out=out),
+                          lambda lo, c: ops.pack_weights_bf16(w, 1, c_out, c, transpose=True, src_width=c_in, src_off=lo),
+                          c_in, s.n_in, dy.device)
+    if s.kind == 'k3':
+        return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, nbr=s.table, n_offsets=27, nbr_ks=s.n_in, nbr_os=1,
+                                                           row_order=s.row_order, out=out),
+                          lambda lo, c: ops.pack_weights_bf16(w, 27, c_out, c, transpose=True, flip=True, src_width=c_in, src_off=lo),
+                          c_in, s.n_in, dy.device)
+    pack8 = lambda lo, c: ops.pack_weights_bf16(w, 8, c_out, c, transpose=True, src_width=c_in, src_off=lo)      # noqa: E731
+    if s.kind == 'k2s2':
+        return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_out, groups=8, out_map=s.table, om_os=8, om_gs=1,
+                                                           out_rows=s.n_in, out=out), pack8, c_in, s.n_in, dy.device)
+    if s.kind == 'k2s2T':
+        return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, nbr=s.table, n_offsets=8, nbr_ks=1, nbr_os=8, out=out),
+                          pack8, c_in, s.n_in, dy.device)
+    # 'gen': dY [8m, c_out] read as [m, 8 c_out]; the eight packed images W[g]^T side by side ARE the image of [8 c_out, c_in]
+    return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy.view(s.n_in, 8 * c_out), wp, c, s.n_in, out=out), pack8, c_in, s.n_in, dy.device)
+
+
+def _weight_grad_bf16(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
+    if s.kind == 'k1':
+        dw = ops.conv_wgrad_bf16(x, dy, s.n_in)
+    elif s.kind == 'k3':
+        dw = ops.conv_wgrad_bf16(x, dy, s.n_in, nbr=s.table, n_offsets=27, nbr_ks=s.n_in, nbr_os=1, row_order=s.row_order)
+    elif s.kind == 'k2s2':
+        dw = ops.conv_wgrad_bf16(x, dy, s.n_out, nbr=s.table, n_offsets=8, nbr_ks=1, nbr_os=8)
+    elif s.kind == 'k2s2T':
+        dw = ops.conv_wgrad_bf16(x, dy, s.n_in, groups=8, out_map=s.table, om_os=8, om_gs=1)
+    else:                                                                                                # 'gen'
+        dw = ops.conv_wgrad_bf16(x, dy, s.n_in, groups=8)
+    return dw.view(w.shape)
+
+
+def _backward_operands(x: torch.Tensor, g: torch.Tensor, w: torch.Tensor, s: ConvSpec):
+    """-> (g for the input gradient, g for the weight gradient): where the forward ran in bfloat16 (it saved a bf16 x), g is cast ONCE
+    and serves both products; an input gradient whose mirrored shape has no bf16 kernel keeps the fp32 g"""
+    if x.dtype is not torch.bfloat16:
+        return g, g
+    gb = ops.cast_bf16(g)
+    return (gb if _bf16_input_grad_ok(w.shape[-2], w.shape[-1], s.kind) else g), gb
 
 
 def _strided_rows(t: torch.Tensor) -> bool:
@@ -63,6 +189,8 @@ def _one_channel_ok(c_in: int, c_out: int) -> bool:
 
 def _forward(x: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
     c_in, c_out = w.shape[-2], w.shape[-1]
+    if x.dtype is torch.bfloat16:
+        return _forward_bf16(x, w, s)
     if s.kind == 'k1':
         return ops.conv_f32(x, w.reshape(c_in, c_out), c_out, s.n_in, pack=PACK)
     if s.kind == 'k3' and _one_channel_ok(c_in, c_out):
@@ -105,6 +233,8 @@ def _wide(call, wt: torch.Tensor, width: int, rows: int, device) -> torch.Tensor
 
 def _input_grad(dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
     c_in, c_out = w.shape[-2], w.shape[-1]
+    if dy.dtype is torch.bfloat16:
+        return _input_grad_bf16(dy, w, s)
     if s.kind == 'tab':
         raise NotImplementedError('input gradient through a general lookup-table convolution')
     if s.kind == 'k1':
@@ -140,6 +270,8 @@ def _input_grad(dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
 
 
 def _weight_grad(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
+    if x.dtype is torch.bfloat16:
+        return _weight_grad_bf16(x, dy, w, s)
     if s.kind == 'k1':
         dw = ops.conv_wgrad(x, dy, s.n_in)
     elif s.kind == 'k3':
@@ -174,6 +306,8 @@ class SparseConvFn(torch.autograd.Function):
     def forward(ctx, x: torch.Tensor, w: torch.Tensor, spec: ConvSpec):
         x = x.contiguous()
         w = w.contiguous()
+        if _bf16_forward_ok(w.shape[-2], w.shape[-1], spec.kind):
+            x = ops.cast_bf16(x)                   # cast once; the bf16 copy is what the backward keeps
         ctx.save_for_backward(x, w)
         ctx.spec = spec
         return _forward(x, w, spec)
@@ -182,9 +316,9 @@ class SparseConvFn(torch.autograd.Function):
     def backward(ctx, dy: torch.Tensor):
         x, w = ctx.saved_tensors
         s = ctx.spec
-        dy = dy.contiguous()
-        dx = _input_grad(dy, w, s) if ctx.needs_input_grad[0] else None
-        dw = _weight_grad(x, dy, w, s) if ctx.needs_input_grad[1] else None
+        g_dx, g_dw = _backward_operands(x, dy.contiguous(), w, s)
+        dx = _input_grad(g_dx, w, s) if ctx.needs_input_grad[0] else None
+        dw = _weight_grad(x, g_dw, w, s) if ctx.needs_input_grad[1] else None
         return dx, dw, None
 
 
@@ -204,7 +338,10 @@ class SparseConvActFn(torch.autograd.Function):
         c_in, c_out = w.shape[-2], w.shape[-1]
         b = None if bias is None else bias.reshape(-1)
         kw = dict(bias=b, act=act, slope=slope)
-        if spec.kind == 'k1':
+        if _bf16_forward_ok(c_in, c_out, spec.kind):
+            x = ops.cast_bf16(x)
+            y = _forward_bf16(x, w, spec, **kw)
+        elif spec.kind == 'k1':
             y = ops.conv_f32(x, w.reshape(c_in, c_out), c_out, spec.n_in, pack=PACK, **kw)
         elif spec.kind == 'k3' and _one_channel_ok(c_in, c_out):
             y = _k3_one_channel(x, w, spec, **kw)
@@ -235,8 +372,9 @@ class SparseConvActFn(torch.autograd.Function):
         else:       # the epilogue kernel reads rows at any stride (a column slice of a concatenation's gradient) and writes g packed
             g, dbias, dslope = ops.epilogue_bwd(y, dy if _strided_rows(dy) else dy.contiguous(), ctx.act, slope if ctx.has_slope else None,
                                                 want_b, want_s)
-        dx = _input_grad(g, w, s) if ctx.needs_input_grad[0] else None
-        dw = _weight_grad(x, g, w, s) if ctx.needs_input_grad[1] else None
+        g_dx, g_dw = _backward_operands(x, g, w, s)
+        dx = _input_grad(g_dx, w, s) if ctx.needs_input_grad[0] else None
+        dw = _weight_grad(x, g_dw, w, s) if ctx.needs_input_grad[1] else None
         if dbias is not None:
             dbias = dbias.view(ctx.bias_shape)
         if dslope is not None:
@@ -260,8 +398,13 @@ class LinearActFn(torch.autograd.Function):
         x = x.contiguous()
         c_out, c_in = weight.shape
         n = x.shape[0]
-        y = ops.conv_f32(x, weight.detach().t().contiguous(), c_out, n, bias=None if bias is None else bias.reshape(-1), act=act, slope=slope,
-                         pack=PACK)
+        if _bf16_forward_ok(c_in, c_out, 'k1'):
+            x = ops.cast_bf16(x)                   # B[ci][co] = weight[co][ci]: packed transposed straight from the parameter
+            y = ops.conv_bf16(x, ops.pack_weights_bf16(weight.detach().contiguous(), 1, c_in, c_out, transpose=True), c_out, n,
+                              bias=None if bias is None else bias.reshape(-1), act=act, slope=slope)
+        else:
+            y = ops.conv_f32(x, weight.detach().t().contiguous(), c_out, n, bias=None if bias is None else bias.reshape(-1), act=act,
+                             slope=slope, pack=PACK)
         ctx.save_for_backward(x, weight, y, slope if slope is not None else x.new_empty(0))
         ctx.act, ctx.has_bias, ctx.has_slope = act, bias is not None, slope is not None
         ctx.bias_shape = None if bias is None else bias.shape
@@ -280,9 +423,23 @@ class LinearActFn(torch.autograd.Function):
             g, dbias, dslope = ops.epilogue_bwd(y, dy if _strided_rows(dy) else dy.contiguous(), ctx.act, slope if ctx.has_slope else None,
                                                 want_b, want_s)
         dx = dw = None
-        if ctx.needs_input_grad[0]:
+        if x.dtype is torch.bfloat16:
+            gb = ops.cast_bf16(g)
+            wd = weight.detach().contiguous()
+            if ctx.needs_input_grad[0]:
+                if _bf16_input_grad_ok(c_in, c_out, 'k1'):         # B[co][ci] = weight[co][ci]: the stored layout, 128 columns a launch
+                    dx = _wide_bf16(lambda wp, c, out: ops.conv_bf16(gb, wp, c, n, out=out),
+                                    lambda lo, c: ops.pack_weights_bf16(wd, 1, c_out, c, src_width=c_in, src_off=lo), c_in, n, dy.device)
+                else:
+                    dx = _wide(lambda wt, c, out: ops.conv_f32(g, wt, c, n, out=out, pack=PACK), wd, c_in, n, dy.device)
+            if ctx.needs_input_grad[1]:
+                if ops.conv_bf16_supported(c_out, c_in):            # dW [c_out, c_in] = g^T x, the stored orientation
+                    dw = ops.conv_wgrad_bf16(gb, x, n).view(c_out, c_in)
+                else:
+                    dw = ops.conv_wgrad_bf16(x, gb, n).view(c_in, c_out).t()
+        elif ctx.needs_input_grad[0]:
             dx = _wide(lambda wt, c, out: ops.conv_f32(g, wt, c, n, out=out, pack=PACK), weight.detach(), c_in, n, dy.device)
-        if ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1] and x.dtype is not torch.bfloat16:
             if c_in in (32, 64, 128) and c_out % 64 == 0:        # shapes the matrix-core gradient kernel takes with the operands swapped
                 dw = ops.conv_wgrad(g, x, n).view(c_out, c_in)
             else:                                                # (a 256-wide input: its own orientation, transposed as a view)

@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import hipops as ops
+from .autograd import conv_autocast      # noqa: F401 -- mixed-precision context of the training convolutions, exported beside the Minkowski* names
 
 
 # ---------------------------------------------------------------------------------------------------------------

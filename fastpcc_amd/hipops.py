@@ -120,6 +120,14 @@ _SIGS = {
     'fpcc_int_level_trunk': (_i64, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i64, _vp]),
     'fpcc_int_level_expand': (_i64, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_octree_children': (_i64, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'fpcc_conv_bf16_supported': (_i32, [_i32, _i32, _i32, _i32]),
+    'fpcc_cast_f32_bf16': (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    'fpcc_conv_pack_weights_bf16': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    'fpcc_conv_bf16': (_i32, [_vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i64, _i32,
+                              _vp, _f32, _vp, _vp, _i64, _vp]),
+    'fpcc_conv_wgrad_bf16_ws_bytes': (_i64, [_i32, _i32, _i32, _i32, _i64]),
+    'fpcc_conv_wgrad_bf16': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp,
+                                    _i32, _vp, _i64, _vp]),
 }
 HIP_SYMBOLS = tuple(_SIGS) + ('fpcc_last_error',)
 _BLOCKING_ENTRY_POINTS = ('fpcc_hilbert3d_encode', 'fpcc_conv_debug_stamps', 'fpcc_conv_i8_debug_stamps', 'fpcc_int_init')
@@ -930,6 +938,94 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch
                               _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs, groups, n,
                               _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
                               _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# mixed-precision training: bfloat16 operands on the bf16 MFMA, fp32 accumulation and results (conv_bf16.hip)
+
+@functools.lru_cache(maxsize=None)
+def conv_bf16_supported(c_in: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
+    """shapes fpcc_conv_bf16 / fpcc_conv_wgrad_bf16 take; every other shape stays on the fp32 kernels"""
+    return bool(lib().fpcc_conv_bf16_supported(int(c_in), int(c_out), int(n_offsets), int(groups)))
+
+
+def _rows2d_bf16(t: torch.Tensor, name: str):
+    if t.dim() != 2 or t.dtype != torch.bfloat16 or not t.is_cuda or t.stride(1) != 1:
+        raise TypeError(f'{name} must be a 2-D bfloat16 GPU tensor with unit column stride')
+    return t.data_ptr(), t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)))
+
+
+def cast_bf16(x: torch.Tensor) -> torch.Tensor:
+    """fp32 rows (any row pitch of whole 16-byte pieces) -> a packed bfloat16 matrix, round to nearest even (fpcc_cast_f32_bf16)"""
+    p, c, ld = _rows2d(x, 'x')
+    n = x.shape[0]
+    out = torch.empty((n, c), dtype=torch.bfloat16, device=x.device)
+    _ok(lib().fpcc_cast_f32_bf16(p, ld, n, c, out.data_ptr(), c, _stream()))
+    return out
+
+
+def pack_weights_bf16(w: torch.Tensor, n_mats: int, c_in: int, c_out: int, *, transpose: bool = False, flip: bool = False,
+                      src_width: Optional[int] = None, src_off: int = 0) -> torch.Tensor:
+    """fp32 weights -> the bf16 B-operand image of n_mats matrices [c_in, c_out] (fpcc_conv_pack_weights_bf16).  The source holds
+    n_mats matrices [c_in][src_width] (or, transposed, [src_width][c_in]) of which columns (rows) src_off .. src_off + c_out are taken;
+    flip mirrors the matrix order"""
+    width = c_out if src_width is None else int(src_width)
+    w = w.detach()
+    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous() or w.numel() != n_mats * c_in * width:
+        raise ValueError(f'weights must be contiguous fp32 with {n_mats} x {c_in} x {width} elements, got {tuple(w.shape)}')
+    out = torch.empty(n_mats * c_in * c_out, dtype=torch.bfloat16, device=w.device)
+    _ok(lib().fpcc_conv_pack_weights_bf16(w.data_ptr(), n_mats, c_in, c_out, int(transpose), int(flip), width, int(src_off),
+                                          out.data_ptr(), _stream()))
+    return out
+
+
+def conv_bf16(x: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out: int, *, nbr: Optional[torch.Tensor] = None, n_offsets: int = 1,
+              nbr_ks: int = 0, nbr_os: int = 1, bias: Optional[torch.Tensor] = None, groups: int = 1,
+              out_map: Optional[torch.Tensor] = None, om_os: int = 0, om_gs: int = 1, out: Optional[torch.Tensor] = None,
+              out_rows: Optional[int] = None, act: int = ACT_NONE, slope: Optional[torch.Tensor] = None, clip: float = 0.0,
+              row_order: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_f32 on bfloat16 rows and packed bf16 weights (pack_weights_bf16), fp32 out; see fpcc_conv_bf16"""
+    px, c_in, ldx = _rows2d_bf16(x, 'x')
+    if w_packed.dtype != torch.bfloat16 or not w_packed.is_cuda or not w_packed.is_contiguous() or \
+            w_packed.numel() != groups * n_offsets * c_in * c_out:
+        raise ValueError(f'packed weights must hold {groups} x {n_offsets} x {c_in} x {c_out} bfloat16')
+    if out is None:
+        rows = out_rows if out_rows is not None else n_out * groups
+        out = torch.empty((rows, c_out), dtype=torch.float32, device=x.device)
+    po, co, ldo = _rows2d(out, 'out')
+    if co != c_out:
+        raise ValueError('output width mismatch')
+    if om_os == 0:
+        om_os = groups
+    _ok(lib().fpcc_conv_bf16(px, c_in, ldx, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os, w_packed.data_ptr(),
+                             _dev(bias, torch.float32, 'bias', True), c_out, groups, _dev(out_map, torch.int32, 'out_map', True),
+                             om_os, om_gs, po, ldo, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
+                             _dev(row_order, torch.int32, 'row_order', True), None, 0, _stream()))
+    return out
+
+
+def conv_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch.Tensor] = None, n_offsets: int = 1,
+                    nbr_ks: int = 0, nbr_os: int = 1, out_map: Optional[torch.Tensor] = None, om_os: int = 0, om_gs: int = 1,
+                    groups: int = 1, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+                    row_order: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv_wgrad on bfloat16 x and dy, dW fp32 [groups, n_offsets, c_in, c_out]; see fpcc_conv_wgrad_bf16"""
+    px, c_in, ldx = _rows2d_bf16(x, 'x')
+    pd, c_out, ldy = _rows2d_bf16(dy, 'dy')
+    if out is None:
+        out = torch.empty((groups, n_offsets, c_in, c_out), dtype=torch.float32, device=x.device)
+        accumulate = False
+    if not out.is_contiguous() or out.numel() != groups * n_offsets * c_in * c_out or out.dtype != torch.float32:
+        raise ValueError('dw must be contiguous fp32 [groups, n_offsets, c_in, c_out]')
+    L = lib()
+    need = _ok(L.fpcc_conv_wgrad_bf16_ws_bytes(c_in, c_out, n_offsets, groups, n))
+    ws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
+    if om_os == 0:
+        om_os = groups
+    _ok(L.fpcc_conv_wgrad_bf16(px, c_in, ldx, pd, c_out, ldy, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os,
+                               _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs, groups, n,
+                               _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
+                               _stream()))
     return out
 
 

@@ -12,6 +12,7 @@ split as 8 / N clouds per rank; the only collective is the gradient all-reduce o
 in DDP buckets, overlapped with the rest of the backward pass.
 """
 import contextlib
+import dataclasses
 import time
 from dataclasses import dataclass, field
 from typing import Dict, Iterator, List, Optional, Sequence, Tuple
@@ -22,7 +23,7 @@ import torch.distributed as dist
 from torch.nn.parallel import DistributedDataParallel as DDP
 
 from . import replicas
-from .engine import refresh_prelu_cache
+from .engine import conv_autocast, refresh_prelu_cache
 from .data import PCData
 
 _EXTRA_STATE_SUFFIX = '_extra_state'
@@ -43,6 +44,19 @@ class TrainConfig:
     bucket_cap_mb: Optional[int] = None
     find_unused_parameters: bool = False
     fused_optimizer: bool = True                          # torch.optim's fused (one launch, device-side step counters) Adam / AdamW
+    amp_dtype: str = ''                                   # '' | 'bfloat16': operand dtype of the training convolutions (lib/config.py:29)
+
+    def __post_init__(self):
+        # the reference accepts '', 'float16' and 'bfloat16' (lib/config.py:69).  float16 would need a GradScaler and brings nothing on
+        # this hardware (the bf16 and f16 matrix rates are equal), so it is refused by name rather than silently run in fp32.
+        if self.amp_dtype == 'float16':
+            raise ValueError("train.amp_dtype: only 'bfloat16' is provided ('float16' needs loss scaling and is no faster here)")
+        if self.amp_dtype not in ('', 'bfloat16'):
+            raise ValueError(f"train.amp_dtype must be '' or 'bfloat16', got {self.amp_dtype!r}")
+
+    @property
+    def amp_torch_dtype(self) -> Optional[torch.dtype]:
+        return torch.bfloat16 if self.amp_dtype == 'bfloat16' else None
 
 
 def unwrap(model: torch.nn.Module) -> torch.nn.Module:
@@ -114,7 +128,8 @@ class Trainer:
         batch.training_step = self.optimisation_step
         sync_off = isinstance(self.model, DDP) and not update
         with self.model.no_sync() if sync_off else contextlib.nullcontext():
-            out = self.model(batch)
+            with conv_autocast(self.cfg.amp_torch_dtype):     # the forward decides; the backward uses what the forward saved
+                out = self.model(batch)
             (out['loss'] / acc).backward()
         if update:
             for opt, clip in zip(self.optimizers, self.cfg.max_grad_norm):
@@ -308,10 +323,12 @@ def ddp_training_record(steps: int, warmup: int, device: torch.device, resolutio
 
 
 def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Optional[TrainConfig] = None,
-          model_name: str = 'baseline_r1') -> Optional[dict]:
+          model_name: str = 'baseline_r1', *, amp_dtype: str = '') -> Optional[dict]:
     """times `steps` optimisation steps of lossy_coord_v2/<model_name> (baseline_r1 | r3 | r5) on synthetic ShapeNet-like batches;
-    rank 0 returns the result record, other ranks None"""
+    rank 0 returns the result record, other ranks None.  amp_dtype ('' | 'bfloat16') overrides cfg.amp_dtype when given"""
     cfg = cfg or TrainConfig()
+    if amp_dtype:
+        cfg = dataclasses.replace(cfg, amp_dtype=amp_dtype)
     rank, world, local = replicas.env_rank()
     if world != gpus:
         raise SystemExit(f'--gpus {gpus} but WORLD_SIZE={world}')
@@ -327,7 +344,8 @@ def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Option
     return {'metric': f'training clouds/sec, lossy_coord_v2 {model_name} (DDP)', 'value': rec['clouds_per_s'],
             'unit': 'clouds/s', 'n_gpus': world, 'steps': steps, 'warmup': warmup,
             'ms_per_step': rec['ms_per_step'], 'higher_is_better': True, 'scaling': 'strong',
-            'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+            'vs_baseline': None, 'dtype': 'f32' if not cfg.amp_dtype else 'f32 master weights, bf16 conv operands',
+            'amp_dtype': cfg.amp_dtype, 'data': 'synthetic',
             'config': {'workload': f'lossy_coord_v2/{model_name} training, global batch {cfg.batch_size} ShapeNet-like clouds at '
                                    f'{resolution}^3 (cfg#5), {cfg.batch_size // world} per rank',
                        'parallelism': f'ddp{world}', 'voxels_per_step': rec['voxels_per_step'],

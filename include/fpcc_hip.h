@@ -741,6 +741,53 @@ int fpcc_simple_dec_pop_dev(int32_t *state, const uint8_t *stream, int64_t strea
                             int64_t n_rows, int64_t width, uint16_t *symbols_out, int64_t n, int32_t *children_out,
                             void *hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------------ */
+/* Mixed-precision TRAINING: bfloat16 operands, fp32 accumulation (conv_bf16.hip).  Never used by inference.       */
+/* ------------------------------------------------------------------------------------------------------------ */
+/* The operators of fpcc_conv_f32 / fpcc_conv_wgrad_f32 with both operands rounded to bfloat16 (round to nearest even from fp32),
+ * products accumulated in fp32 on v_mfma_f32_32x32x16_bf16 and fp32 results.  The summation order is a function of the shape alone
+ * (forward: one chain from zero, offsets ascending, 16-channel steps ascending inside an offset; layers of 8 or more offsets: the four
+ * contiguous offset groups [ceil(g K / 4), ceil((g + 1) K / 4)), each such a chain, added as ((g0 + g1) + g2) + g3;
+ * weight gradient: rows in position order inside a row split, splits added in ascending
+ * order); no atomics, so the same call gives the same bits twice.  These bits are NOT those of
+ * the fp32 entries and are not part of any stream format.  bf16 values travel as uint16_t (the upper half of the fp32 pattern).
+ *
+ * The entries take c_in a multiple of 32, c_out in {32, 64, 128}, 1 <= n_offsets <= 32, 1 <= groups <= 8.
+ * fpcc_conv_bf16_supported: 1 for the shapes training ROUTES to them -- those, less the shapes measured no faster than the fp32 entries
+ * on the maps of a training step (the per-point layer 64 -> 128; profiles/r07/amp_bf16.md) -- else 0: every other shape stays fp32. */
+int fpcc_conv_bf16_supported(int c_in, int c_out, int n_offsets, int groups);
+/* dst[r][0..c) = bf16(src[r][0..c)), r < n.  c a multiple of 8; ld (floats) a multiple of 4, ldd (bf16) of 8; both pointers 16-byte
+ * aligned.  A tensor is converted once per use as an operand, not once per gathered row. */
+int fpcc_cast_f32_bf16(const float *src, int64_t ld, int64_t n, int c, uint16_t *dst, int64_t ldd, void *stream);
+/* The fp32 master weights as the B-operand image of the 32x32x16 MFMA, n_mats * c_in * c_out bf16:
+ *     w_packed[m][s][nb][lane][j] = B_m[16 s + 8 (lane >> 5) + j][32 nb + (lane & 31)]       s < c_in / 16, nb < c_out / 32, j < 8
+ * so a lane's fragment is one 16-byte load.  B_m is cut from the source as
+ *     transpose == 0:  B_m[k][c] = w[src(m)][k][src_off + c]      source matrices [c_in][src_width]
+ *     transpose != 0:  B_m[k][c] = w[src(m)][src_off + c][k]      source matrices [src_width][c_in]
+ * with src(m) = flip ? n_mats - 1 - m : m: the weights of an input-gradient convolution, W'[k] = W[mirror(k)]^T, and a 128-column
+ * slice of them are packed straight from W.  c_in a multiple of 16, c_out of 32.  n_mats images of c_in = C stacked are ONE image of
+ * c_in = n_mats * C (the packed GEMM of a generated set's input gradient). */
+int fpcc_conv_pack_weights_bf16(const float *w, int64_t n_mats, int c_in, int c_out, int transpose, int flip, int src_width,
+                                int src_off, uint16_t *w_packed, void *stream);
+/* fpcc_conv_f32 on bf16 rows x [*, c_in] (row stride ldx bf16, a multiple of 8) and packed weights of groups * n_offsets matrices;
+ * nbr / out_map / row_order / bias / act / slope / clip as there, out fp32.  Output-stationary: a wave owns 32 output rows and all
+ * column blocks and gathers its A operand straight to registers (16 bytes of a neighbour's row per 16-channel step); a block of 32
+ * rows none of which has an offset skips it.  The four offset groups of a layer of 8 or more offsets go to the four waves of a workgroup
+ * and are added from LDS in that fixed order.  ws is not used (NULL, 0). */
+int fpcc_conv_bf16(const uint16_t *x, int c_in, int ldx, const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                   const uint16_t *w_packed, const float *bias, int c_out, int groups,
+                   const int32_t *out_map, int64_t om_os, int64_t om_gs, float *out, int ldo, int64_t n_out,
+                   int act, const float *slope, float clip, const int32_t *row_order, void *ws, int64_t ws_bytes, void *stream);
+/* fpcc_conv_wgrad_f32 on bf16 rows x and dy (strides multiples of 8), dw fp32.  The reduction runs over rows, so the MFMA K dimension
+ * is the row index: per block of 64 rows the gathered x rows and the dy rows are written transposed to LDS and read back as 16-byte
+ * operand fragments; a block none of whose rows has the offset is skipped.  ws: fpcc_conv_wgrad_bf16_ws_bytes() bytes of fp32
+ * partial sums per row split, reduced in ascending split order. */
+int64_t fpcc_conv_wgrad_bf16_ws_bytes(int c_in, int c_out, int n_offsets, int groups, int64_t n);
+int fpcc_conv_wgrad_bf16(const uint16_t *x, int c_in, int ldx, const uint16_t *dy, int c_out, int ldy,
+                         const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                         const int32_t *out_map, int64_t om_os, int64_t om_gs, int groups, int64_t n,
+                         const int32_t *row_order, float *dw, int accumulate, void *ws, int64_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
