@@ -882,6 +882,8 @@ __global__ __launch_bounds__(256, 3) void k_conv_wave22(ConvArgs a, const float 
 // So per block and group the running sum receives either the block's own order-1 partial sum or +0, in group order.
 // The price: a unit executes every offset either of its blocks has (pattern row order puts like blocks side by side), and a launch
 // has half as many units -- for large maps with a row order (launch_grouped).
+// (Leaving out the MFMAs of a block that lacks the stage's offset -- scalar branches around them, loads unconditional -- compiles without
+// scratch or vmcnt(0), but the 27-offset launches on maps >= 200 K rows took 1.3-2.5 % MORE time with it: profiles/r08/discarded_work.md.)
 __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_units) {
     constexpr int CH = 32, G8 = 4;
     constexpr int SB = 0x6;                         // the next stage's address arithmetic may float between the MFMAs (k_conv_wave)
@@ -1134,15 +1136,16 @@ int launch_mfma_cfg(ConvArgs a, hipStream_t s) {
 // which is therefore refused unless the process runs with FPCC_EXPERIMENT=1 and has no environment variable.
 // kKnobStamps (0 | 16: the stamped builds of the grouped and the LDS-operand kernel, same bits) has no environment variable either.
 enum { kKnobWaveOn = 0, kKnobWaveNbw = 1, kKnobWaveSb = 2, kKnobStamps = 3, kKnobGroupedFoldRows = 4, kKnobMfmaCfg = 5, kKnobPointwiseRows = 6,
-       kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobFold64 = 13, kKnobCount = 14 };
-int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+       kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobFold64 = 13, kKnobK2s2tSparse = 14,
+       kKnobCount = 15 };
+int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 int knob(int k) {
     if (g_knob[k] < 0) {
         static const char *names[kKnobCount] = {"FPCC_CONV_WAVE", "FPCC_WAVE_NBW", "FPCC_WAVE_SB", "", "FPCC_GROUPED_FOLD_ROWS",
                                                 "FPCC_MFMA_TILE", "FPCC_POINTWISE_MIN_ROWS", "", "FPCC_GROUPED_NBW",
                                                 "FPCC_WAVE22_MIN_ROWS", "FPCC_LDS_MIN_ROWS", "FPCC_LDS_ROW_BLOCKS",
-                                                "FPCC_CONV_PERSIST", "FPCC_CONV_FOLD64"};
-        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0, 0};
+                                                "FPCC_CONV_PERSIST", "FPCC_CONV_FOLD64", "FPCC_K2S2T_SPARSE"};
+        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0, 0, 0};
         const char *e = names[k][0] ? getenv(names[k]) : nullptr;
         g_knob[k] = e ? atoi(e) : defaults[k];
     }
@@ -1284,8 +1287,8 @@ int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s
     return check_hip(hipGetLastError(), "k_conv_wave(folded)");
 }
 
-// Folded 64 x 64 wave units (k_conv_fold64) for the folded launches of the shapes they were measured on -- 27 offsets, 64 | 128
-// output channels: knob 13 / FPCC_CONV_FOLD64 = 0: on maps with a row order (pattern order puts like blocks side by side) of at
+// Folded 64 x 64 wave units (k_conv_fold64) for the folded launches of the shapes they were measured on -- 27 offsets (3x3x3) or 8
+// (stride-2 2x2x2, profiles/r07/fold64.md section 4), 64 | 128 output channels: knob 13 / FPCC_CONV_FOLD64 = 0: on maps with a row order (pattern order puts like blocks side by side) of at
 // least kFold64Rows rows, 1: never (the 32-row folded units), 2: on every folded launch of such a shape.  Every other shape, maps
 // without a row order and the persistent folded form (knob 12) keep the 32-row units.
 // Threshold from the bench's own maps (profiles/r07/fold64.md): 286 K, 1.13 M and 4.36 M rows gain at both widths; there is no
@@ -1293,7 +1296,7 @@ int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s
 constexpr int64_t kFold64Rows = 200 * 1024;
 std::atomic<long long> g_fold64_launches{0};       // fpcc_conv_fold64_launches(): which unit a launch took (tests)
 inline bool use_fold64(const ConvArgs &a, int nbt) {
-    if ((nbt != 2 && nbt != 4) || a.n_off != kMaxOffsets || knob(kKnobPersist) > 0) return false;
+    if ((nbt != 2 && nbt != 4) || (a.n_off != kMaxOffsets && a.n_off != 8) || knob(kKnobPersist) > 0) return false;
     const int v = knob(kKnobFold64);
     if (v) return v >= 2;
     return a.row_order && a.n_out >= kFold64Rows;
@@ -1968,6 +1971,134 @@ extern "C" int fpcc_conv_row_keys(const int32_t *nbr, int n_offsets, int64_t nbr
     hipLaunchKernelGGL(k_conv_row_keys, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), nbr, n_offsets, nbr_ks,
                        nbr_os, n, window_log2, keys_out, masks_out);
     return check_hip(hipGetLastError(), "k_conv_row_keys");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Transposed 2x2x2 stride-2 convolution onto an EXISTING child map, over the children that exist.  The groups = 8 / out_map form of
+// fpcc_conv_f32 evaluates all 8 octant kernels for every parent row and drops the rows whose out_map entry is -1; a surface parent
+// has ~3.9 of its 8 children, so half of that work is thrown away.  Here the layer is a gather-GEMM over the child rows:
+// out[c] = act(x[parent_of[c]] . W[octant(c)] + b), run by the order-1 wave kernel on a one-hot table [children][8] (the parent's row
+// in column octant(c), -1 elsewhere).  A 32-row block executes every offset any of its rows has, and in Morton order a block of
+// children holds all 8 octants: so the children of a window of 2^window_log2 consecutive rows are walked ordered by octant (a stable
+// counting sort, the parents' rows of a window stay L2-resident) and a block then has ONE octant, except the <= 8 blocks per window
+// that straddle two classes.  Every output row is the same single FMA chain as before (a mixed block adds fma(0, w, acc) terms).
+namespace fpcc {
+namespace {
+// Threshold of knob 14 = 0, by the launches' sizes in the committed traces (profiles/r07/forced_fold64_conv_launches.txt): the form
+// saves at most half of the groups = 8 launch -- ~0.45 of 0.90 ms on the 1.13 M-child map, ~0.11 of 0.23 ms at 286 K children, but
+// 0.035 of 0.07 ms at 71 K and 0.015 of 0.03 ms at 17 K children, which is what the order kernel's launch (one workgroup per window,
+// two serial passes over its tiles) costs on a map that small.  From 200 K children, the bound the 64-row folded units use.
+constexpr int64_t kK2s2tSparseRows = 200 * 1024;
+std::atomic<long long> g_k2s2t_sparse_launches{0};
+
+// one workgroup per window: 8 bins, a prefix sum, a scatter in tiles of 1024 rows (two barriers per tile).  octant(c) is the column
+// of c in its parent's child_row line; a child its parent does not list (a table that is not one) is filed under octant 0 with an
+// empty table row, so that positions stay a permutation of the window whatever the input.
+__global__ __launch_bounds__(1024) void k_k2s2t_order(const int32_t *__restrict__ parent_of, const int32_t *__restrict__ child_row,
+                                                      int64_t n, int64_t n_parents, int window_log2, int32_t *__restrict__ order,
+                                                      int32_t *__restrict__ table) {
+    __shared__ uint32_t s_cnt[16][8];
+    __shared__ uint32_t s_base[2][8];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int64_t w0 = (int64_t)blockIdx.x << window_log2;
+    const int64_t w1 = min(n, w0 + ((int64_t)1 << window_log2));
+    auto octant_of = [&](int64_t c, int32_t &par) {
+        par = parent_of[c];
+        if (par < 0 || par >= n_parents) { par = -1; return 0; }
+        const int4 *line = reinterpret_cast<const int4 *>(child_row + (int64_t)par * 8);
+        const int4 lo = line[0], hi = line[1];
+        const int32_t e[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        int o = -1;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o = e[j] == (int32_t)c ? j : o;
+        if (o < 0) { par = -1; o = 0; }
+        return o;
+    };
+    if (t < 8) s_base[0][t] = 0;
+    __syncthreads();
+    for (int64_t c = w0 + t; c < w1; c += 1024) {
+        int32_t par;
+        atomicAdd(&s_base[0][octant_of(c, par)], 1u);
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t run = 0;
+        for (int b = 0; b < 8; ++b) { const uint32_t k = s_base[0][b]; s_base[0][b] = run; run += k; }
+    }
+    int cur = 0;
+    for (int64_t base = w0; base < w1; base += 1024, cur ^= 1) {
+        const int64_t c = base + t;
+        int32_t par = -1;
+        const int o = c < w1 ? octant_of(c, par) : 8;
+        uint32_t rank = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const unsigned long long m = __ballot(o == b);
+            if (o == b) rank = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == b) s_cnt[wv][b] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        if (o < 8) {
+            uint32_t before = 0;
+            for (int w = 0; w < wv; ++w) before += s_cnt[w][o];
+            const int64_t pos = w0 + s_base[cur][o] + before + rank;
+            order[pos] = (int32_t)c;
+            int4 *row = reinterpret_cast<int4 *>(table + pos * 8);
+            row[0] = make_int4(o == 0 ? par : -1, o == 1 ? par : -1, o == 2 ? par : -1, o == 3 ? par : -1);
+            row[1] = make_int4(o == 4 ? par : -1, o == 5 ? par : -1, o == 6 ? par : -1, o == 7 ? par : -1);
+        }
+        if (t < 8) {
+            uint32_t total = 0;
+            for (int w = 0; w < 16; ++w) total += s_cnt[w][t];
+            s_base[cur ^ 1][t] = s_base[cur][t] + total;
+        }
+        __syncthreads();
+    }
+}
+
+inline bool k2s2t_shape_ok(int c_in, int c_out) { return c_in >= 32 && c_in % 32 == 0 && (c_out == 32 || c_out == 64 || c_out == 128); }
+}  // namespace
+}  // namespace fpcc
+
+extern "C" int fpcc_conv_k2s2t_use_sparse(int c_in, int c_out, int64_t n_children) {
+    if (!k2s2t_shape_ok(c_in, c_out) || n_children < 1 || n_children > 0x7fffffffll || !knob(kKnobWaveOn)) return 0;
+    const int v = knob(kKnobK2s2tSparse);
+    if (v) return v >= 2;
+    return n_children >= kK2s2tSparseRows;
+}
+
+extern "C" long long fpcc_conv_k2s2t_sparse_launches(void) { return g_k2s2t_sparse_launches.load(std::memory_order_relaxed); }
+
+extern "C" int fpcc_conv_k2s2t_order(const int32_t *parent_of, const int32_t *child_row, int64_t n_children, int64_t n_parents,
+                                     int window_log2, int32_t *order_out, int32_t *table_out, void *stream) {
+    if (n_children < 0 || n_children > 0x7fffffffll || n_parents < 0 || window_log2 < 5 || window_log2 > 24)
+        return fail_arg("conv_k2s2t_order: sizes out of range (window_log2 5..24)");
+    if (n_children == 0) return FPCC_OK;
+    if (!parent_of || !child_row || !order_out || !table_out || !aligned16(child_row) || !aligned16(table_out))
+        return fail_arg("conv_k2s2t_order: null or unaligned pointer");
+    const int64_t windows = (n_children + ((int64_t)1 << window_log2) - 1) >> window_log2;
+    hipLaunchKernelGGL(k_k2s2t_order, dim3((unsigned)windows), dim3(1024), 0, as_stream(stream), parent_of, child_row, n_children,
+                       n_parents, window_log2, order_out, table_out);
+    return check_hip(hipGetLastError(), "k_k2s2t_order");
+}
+
+extern "C" int fpcc_conv_k2s2t_f32(const float *x, int c_in, int ld, const int32_t *table, const int32_t *order,
+                                   const float *w_packed, const float *bias, int c_out, float *out, int ldo, int64_t n_children, int act,
+                                   const float *slope, float clip, void *stream) {
+    LaunchBracket timed(stream);
+    if (n_children < 0 || n_children > 0x7fffffffll || !k2s2t_shape_ok(c_in, c_out))
+        return fail_arg("conv_k2s2t_f32: c_in must be a multiple of 32 and c_out one of 32, 64, 128");
+    if (n_children == 0) return FPCC_OK;
+    if (!x || !table || !order || !w_packed || !out) return fail_arg("conv_k2s2t_f32: null pointer");
+    if (ld < c_in || ldo < c_out || ld % 4) return fail_arg("conv_k2s2t_f32: row stride smaller than the row or no multiple of 4");
+    if (!aligned16(x) || !aligned16(w_packed) || !aligned16(table)) return fail_arg("conv_k2s2t_f32: pointers must be 16-byte aligned");
+    if (act != FPCC_ACT_NONE && act != FPCC_ACT_PRELU && act != FPCC_ACT_RELU) return fail_arg("conv_k2s2t_f32: unknown activation");
+    if (act == FPCC_ACT_PRELU && !slope) return fail_arg("conv_k2s2t_f32: PReLU needs a slope pointer");
+    // order 1 on the plain wave kernel (fpcc_conv_f32_pk would evaluate an 8-offset table with groups == 1 grouped, order 3)
+    ConvArgs a{x, c_in, ld, nullptr, 0, 0, table, 8, 1, 8, w_packed, bias, c_out, 1,
+               nullptr, 0, 0, out, ldo, n_children, act, slope, clip, order};
+    g_k2s2t_sparse_launches.fetch_add(1, std::memory_order_relaxed);
+    return launch_wave(a, w_packed, as_stream(stream));
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -138,7 +138,8 @@ class KernelGenerator:
 class _Map:
     """One coordinate map: sorted unique keys at pyramid level `level` (tensor stride 1 << level)."""
     __slots__ = ('level', 'bits', 'n', 'keys', 'parent', 'parent_of', 'child_row', 'generated', 'nbr27', 'coords',
-                 'gen_child', 'key', 'row_order', 'mask27', 'nbr27_rows', 'nbr27_pos', 'edges', 'k2_order', 'k2_pos')
+                 'gen_child', 'key', 'row_order', 'mask27', 'nbr27_rows', 'nbr27_pos', 'edges', 'k2_order', 'k2_pos', 'k2t_order',
+                 'k2t_table')
 
     def __init__(self, level: int, bits: int, n: int, keys: Optional[torch.Tensor]):
         self.level, self.bits, self.n, self.keys = level, bits, n, keys
@@ -159,6 +160,10 @@ class _Map:
         # their 8 children exist (False: not decided), and child_row with its rows in that order
         self.k2_order = False
         self.k2_pos: Optional[torch.Tensor] = None
+        # transposed 2x2x2 convolution ONTO this map from its parent, over the rows that exist: this map's rows ordered by octant inside
+        # windows (False: not decided; None: the map lacks what the order needs) and, by position, the one-hot table [n, 8] of parent rows
+        self.k2t_order = False
+        self.k2t_table: Optional[torch.Tensor] = None
 
 
 class CoordinateManager:
@@ -435,6 +440,21 @@ class CoordinateManager:
         if src.k2_order is None:
             return None, src.child_row
         return src.k2_order, src.k2_pos
+
+    K2T_WINDOW_LOG2 = ops.K2S2T_WINDOW_LOG2       # rows per window of the transposed layers' octant order
+
+    def _k2t_order(self, dst: _Map):
+        """(order, table) of the transposed 2x2x2 convolution from dst's parent onto `dst` over the children that exist
+        (ops.conv_k2s2t); cached on the map and shared by every such layer onto it.  -> (None, None) when the map does not carry
+        parent_of and child_row for all its rows."""
+        if dst.k2t_order is False:
+            dst.k2t_order = None
+            po, cr = dst.parent_of, dst.child_row
+            if dst.n > 0 and po is not None and cr is not None and dst.parent is not None and po.numel() == dst.n and \
+                    po.dtype == torch.int32 and cr.dtype == torch.int32 and cr.dim() == 2 and tuple(cr.shape) == (dst.parent.n, 8) and \
+                    po.is_contiguous() and cr.is_contiguous():
+                dst.k2t_order, dst.k2t_table = ops.conv_k2s2t_order(po, cr, dst.n, self.K2T_WINDOW_LOG2)
+        return dst.k2t_order, dst.k2t_table
 
     def get_coordinates(self, key: CoordinateMapKey) -> torch.Tensor:
         m = self._map(key)
@@ -907,8 +927,14 @@ class _ConvBase(nn.Module):
             if dst.generated:
                 out = ops.conv_f32(x1, w, c_out, src.n, groups=8, **kw)
             else:
-                out = ops.conv_f32(x1, w, c_out, src.n, groups=8, out_map=dst.child_row, om_os=8, om_gs=1,
-                                   out_rows=dst.n, **kw)
+                order = table = None
+                if x2 is None and ops.conv_k2s2t_use_sparse(x1.shape[1], c_out, dst.n):
+                    order, table = cm._k2t_order(dst)      # over the children that exist: no octant is computed to be dropped
+                if order is not None:
+                    out = ops.conv_k2s2t(x1, w, c_out, order, table, bias=kw['bias'], act=act.kind, slope=act.slope, clip=clip)
+                else:
+                    out = ops.conv_f32(x1, w, c_out, src.n, groups=8, out_map=dst.child_row, om_os=8, om_gs=1,
+                                       out_rows=dst.n, **kw)
         elif self.ks == 1:
             dst = src
             plan = _pad_plan(x1.shape[1], 0 if x2 is None else x2.shape[1], c_out, plan_rows)

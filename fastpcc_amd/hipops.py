@@ -43,6 +43,10 @@ _SIGS = {
                                 _vp, _i64, _i64, _vp, _i32, _i64, _i32, _vp, _f32, _vp, _vp, _i64, _vp]),
     'fpcc_conv_set_tuning': (_i32, [_i32, _i32]),
     'fpcc_conv_fold64_launches': (_i64, []),
+    'fpcc_conv_k2s2t_order': (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    'fpcc_conv_k2s2t_f32': (_i32, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _f32, _vp]),
+    'fpcc_conv_k2s2t_use_sparse': (_i32, [_i32, _i32, _i64]),
+    'fpcc_conv_k2s2t_sparse_launches': (_i64, []),
     'fpcc_conv_debug_stamps': (_i32, [_vp, _i64]),
     'fpcc_conv_i8_debug_stamps': (_i32, [_vp, _i64]),
     'fpcc_time_next_launch': (_i32, [_vp, _vp]),
@@ -516,6 +520,7 @@ KNOB_GROUPED_FOLD_ROWS = 4       # rows from which grouped (order 3) layers run 
 KNOB_GROUPED_OFF, KNOB_GROUPED_NBW, KNOB_WAVE22_ROWS = 7, 8, 9      # 7: experiments only (FPCC_EXPERIMENT=1), changes the summation order
 KNOB_PERSIST = 12     # workgroups per CU of the persistent grouped / folded kernels (0 = off)
 KNOB_FOLD64 = 13      # folded launches on 64 x 64 wave units: 0 = large maps with a row order, 1 = never, 2 = every folded launch
+KNOB_K2S2T_SPARSE = 14  # transposed 2x2x2 convolution over the existing children: 0 = from a child-row threshold, 1 = never, 2 = always
 KNOB_LDS_ROWS, KNOB_LDS_ROW_BLOCKS = 10, 11  # rows from which order-3 layers take both operands through LDS (0 = never); row blocks per workgroup (2 | 3 | 4)
 
 
@@ -694,6 +699,62 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
     _traced_launch(trace, fn, call, {'mfma': bool(conv_order(c1, c2, c_out, n_offsets, groups, n_out)), 'c_in': c1 + c2, 'c_out': c_out,
                                      'n_out': n_out, 'groups': groups, 'n_offsets': n_offsets, 'nbr': nbr,
                                      'nbr_ks': nbr_ks, 'nbr_os': nbr_os})
+    return out
+
+
+def conv_k2s2t_sparse_launches() -> int:
+    """launches of the transposed 2x2x2 convolution over the existing children (conv_k2s2t) by this process so far"""
+    return int(lib().fpcc_conv_k2s2t_sparse_launches())
+
+
+def conv_k2s2t_use_sparse(c_in: int, c_out: int, n_children: int) -> bool:
+    """whether knob KNOB_K2S2T_SPARSE and the shape send a transposed 2x2x2 layer onto a child map of n_children rows to conv_k2s2t"""
+    return bool(lib().fpcc_conv_k2s2t_use_sparse(int(c_in), int(c_out), int(n_children)))
+
+
+K2S2T_WINDOW_LOG2 = 13      # 256 blocks of 32 rows per window, at most 8 of them mixed; one workgroup of the order kernel per window
+
+
+def conv_k2s2t_order(parent_of: torch.Tensor, child_row: torch.Tensor, n_children: int, window_log2: int = K2S2T_WINDOW_LOG2):
+    """-> (order[n_children], table[n_children, 8]) of a child map for conv_k2s2t: the children ordered by octant inside windows of
+    2^window_log2 rows, and by position the one-hot row (parent's row in column octant) the MFMA kernel reads"""
+    dev = child_row.device
+    order = torch.empty(n_children, dtype=torch.int32, device=dev)
+    table = torch.empty((n_children, 8), dtype=torch.int32, device=dev)
+    if parent_of.numel() < n_children or child_row.dim() != 2 or child_row.shape[1] != 8 or not child_row.is_contiguous():
+        raise ValueError('parent_of [n_children] and a contiguous child_row [parents, 8] are needed')
+    _ok(lib().fpcc_conv_k2s2t_order(_dev(parent_of, torch.int32, 'parent_of', n_children == 0), _dev(child_row, torch.int32, 'child_row', True),
+                                    n_children, child_row.shape[0], window_log2, order.data_ptr(), table.data_ptr(), _stream()))
+    return order, table
+
+
+def conv_k2s2t(x: torch.Tensor, w: torch.Tensor, c_out: int, order: torch.Tensor, table: torch.Tensor, *,
+               bias: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: Optional[torch.Tensor] = None,
+               clip: float = 0.0) -> torch.Tensor:
+    """transposed 2x2x2 stride-2 convolution onto an existing child map over the children that exist: out[c] = act(x[parent_of[c]] @
+    w[octant(c)] + bias), bit for bit conv_f32(groups=8, out_map=child_row).  order, table: conv_k2s2t_order of the child map;
+    w [8, c_in, c_out] (a packed copy is kept, as with conv_f32(pack=True))."""
+    px, c_in, ld = _rows2d(x, 'x')
+    n = order.numel()
+    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous() or w.numel() != 8 * c_in * c_out:
+        raise ValueError(f'weights must be contiguous fp32 [8,{c_in},{c_out}], got {tuple(w.shape)}')
+    if table.shape != (n, 8) or not table.is_contiguous():
+        raise ValueError('table must be the contiguous [n_children, 8] table of conv_k2s2t_order')
+    wp = packed_weights(w, c_in, 0, c_out, 1, 8)
+    if wp is None:
+        raise ValueError(f'conv_k2s2t: no MFMA wave-kernel shape ({c_in} -> {c_out})')
+    out = torch.empty((n, c_out), dtype=torch.float32, device=x.device)
+    fn = lib().fpcc_conv_k2s2t_f32
+    call = (px, c_in, ld, _dev(table, torch.int32, 'table', n == 0), _dev(order, torch.int32, 'order', n == 0), wp.data_ptr(),
+            _dev(bias, torch.float32, 'bias', True), c_out, out.data_ptr(), c_out, n, act, _dev(slope, torch.float32, 'slope', True),
+            float(clip), _stream())
+    trace = _current_trace()
+    if trace is None:
+        _untraced_launch(fn, call)
+        return out
+    # the work that is needed: one (child, parent) pair per child row
+    _traced_launch(trace, fn, call, {'mfma': True, 'c_in': c_in, 'c_out': c_out, 'n_out': n, 'groups': 1, 'n_offsets': 8, 'nbr': table,
+                                     'nbr_ks': 1, 'nbr_os': 8, 'flops': 2.0 * n * c_in * c_out})
     return out
 
 

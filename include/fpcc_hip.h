@@ -230,12 +230,34 @@ int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int gr
  *      values above 16 = that many workgroups in all)
  *   4  rows from which the grouped evaluation runs FOLDED -- one wave per unit adds up the four offset groups itself -- instead of on
  *      four waves per unit (FPCC_GROUPED_FOLD_ROWS, default 102400; 0 = never).  Same order 3, same bits.
- *  13  unit of the folded launches of 27-offset layers with 64 | 128 output channels (FPCC_CONV_FOLD64): 0 = 64 x 64 wave units
+ *  13  unit of the folded launches of 27-offset and 8-offset layers with 64 | 128 output channels (FPCC_CONV_FOLD64): 0 = 64 x 64 wave units
  *      (k_conv_fold64) on maps with a row order of at least 204800 rows, 32-row units elsewhere; 1 = 32-row units always; 2 = 64 x 64
- *      units on every such launch.  The persistent form (knob 12) keeps its 32-row units.  Same order 3, same bits. */
+ *      units on every such launch.  The persistent form (knob 12) keeps its 32-row units.  Same order 3, same bits.
+ *  14  transposed 2x2x2 stride-2 convolution onto an existing child map (FPCC_K2S2T_SPARSE), as answered by
+ *      fpcc_conv_k2s2t_use_sparse: 0 = over the existing children (fpcc_conv_k2s2t_f32) from 204800 child rows upwards,
+ *      the groups = 8 / out_map form of fpcc_conv_f32 below; 1 = never; 2 = for every shape the new form covers.  Same bits. */
 int fpcc_conv_set_tuning(int which, int value);
 /* Diagnostics: launches of k_conv_fold64 by this process so far (tests check which unit a forced launch took). */
 long long fpcc_conv_fold64_launches(void);
+/* Transposed 2x2x2 stride-2 convolution onto an EXISTING child map, evaluated over the children that exist:
+ *     out[c] = act(x[parent_of[c]] . W[octant(c)] + bias)      for the n_children rows c of the child map,
+ * instead of all 8 octant kernels for every parent row with the absent ones dropped (fpcc_conv_f32 with groups = 8 and an out_map),
+ * which on a surface computes about twice what it keeps.  Every output row is the same single FMA chain (order 1) either way.
+ * fpcc_conv_k2s2t_order  once per child map: walks the children of every window of 2^window_log2 (5..24) consecutive rows ordered by
+ *     octant (stable counting sort; octant(c) = the column of c in child_row[parent_of[c]][8]) and writes, by position p,
+ *     order_out[p] = the child row and table_out[p][8] = its parent's row in column octant(c), -1 elsewhere (16-byte aligned).  A
+ *     32-row MFMA block of positions then holds one octant, except the <= 8 blocks per window that straddle two classes.
+ * fpcc_conv_k2s2t_f32    the layer: x [parents][c_in] (row stride ld), w_packed = fpcc_conv_pack_weights_f32 of W [8][c_in][c_out],
+ *     out [n_children][c_out] (row stride ldo); c_in a multiple of 32, c_out in {32, 64, 128}.  Timed by fpcc_time_next_launch.
+ * fpcc_conv_k2s2t_use_sparse  1 when knob 14 and the shape select this form for a child map of n_children rows, else 0.
+ * fpcc_conv_k2s2t_sparse_launches  diagnostics: calls of fpcc_conv_k2s2t_f32 that launched, by this process so far (tests). */
+int fpcc_conv_k2s2t_order(const int32_t *parent_of, const int32_t *child_row, int64_t n_children, int64_t n_parents, int window_log2,
+                          int32_t *order_out, int32_t *table_out, void *stream);
+int fpcc_conv_k2s2t_f32(const float *x, int c_in, int ld, const int32_t *table, const int32_t *order, const float *w_packed,
+                        const float *bias, int c_out, float *out, int ldo, int64_t n_children, int act, const float *slope, float clip,
+                        void *stream);
+int fpcc_conv_k2s2t_use_sparse(int c_in, int c_out, int64_t n_children);
+long long fpcc_conv_k2s2t_sparse_launches(void);
 /* Diagnostics (profiles/r04/small_level_stage.md): with knob 3 set to 16 every wave of the grouped kernel leaves 48 64-bit words in
  * `buf` (device memory, n_u64 words; NULL / 0 detaches): s_memtime at kernel entry [0], after the neighbour-table read [1], after the
  * first operands were requested [2], at the top of stage s [3 + min(s, 36)], after the last stage [40], after the partial-sum
