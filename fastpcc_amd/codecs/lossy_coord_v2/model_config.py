@@ -107,3 +107,19 @@ def baseline_r5() -> ModelConfig:
     return ModelConfig(**{**BASELINE_R1, **dict(
         skip_encoding_fea=-1, encoder_channels=(16, 64, 128, 128), decoder_channels=(128, 64, 16), geo_lossl_if_sample=(0, 1) * 4,
         geo_lossl_channels=(128,) * 8 + (1,), bits_loss_factor=1.2, warmup_fea_loss_steps=10000)})
+
+
+def expanded_r3() -> ModelConfig:
+    """config/convolutional/lossy_coord_v2/expanded_r3.yaml:3-4 over baseline_r3: the lossless pyramid widened to 256 channels below
+    its finest level (expanded_r4.yaml:3-4 holds the same line over baseline_r4, which differs in loss weights only: `from_yaml`)"""
+    cfg = baseline_r3()
+    cfg.geo_lossl_channels = (128,) + (256,) * 9 + (1,)
+    return cfg
+
+
+def expanded_r5() -> ModelConfig:
+    """config/convolutional/lossy_coord_v2/expanded_r5.yaml:3-4 over baseline_r5 (expanded_r6.yaml:3-4 over baseline_r6: loss weights
+    only)"""
+    cfg = baseline_r5()
+    cfg.geo_lossl_channels = (128,) + (256,) * 7 + (1,)
+    return cfg

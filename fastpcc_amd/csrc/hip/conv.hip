@@ -19,6 +19,10 @@
 //                 for 16-channel chunks and for transposed maps (out_map).
 //   k_conv_valu   shapes MFMA tiles do not cover (C_out in {1, 8, 16}, C_in = 1 ...): one thread per output row and
 //                 <= 16 output channels, weights through the scalar cache.  Bandwidth-bound, tiny in this codec.
+// The 256-wide layers of the expanded rate points (natural_shape(): C_out = 256, 32-multiple C_in <= 512) keep the summation order of
+// k_conv_valu -- order 0, the natural chain -- but run on k_conv_wave<..., NAT>: the wave kernel with its A pieces exchanged between
+// the half-waves so that the MFMAs take the channels in ascending order, and a packed weight image of its own.  Same bits as
+// k_conv_valu, 7-36 x faster per launch on the levels of a 1 M-voxel frame (profiles/r09/expanded.md); knob 15 chooses.
 // Multi-offset layers with 32-multiple channel counts are evaluated GROUPED (summation order 3 -- part of the stream format, see
 // FPCC_NUMERICS_VERSION): the kernel offsets form four fixed groups, one wave of a workgroup each, partial sums added in group
 // order -- by four waves of a workgroup that meet in LDS (k_conv_wave<..., OG = 4>: maps below 100 K rows, which need the
@@ -240,9 +244,13 @@ __global__ __launch_bounds__(64 * WM * WN, 3) void k_conv_mfma(ConvArgs a) {
 // VALU path: thread = (output row, group, block of JB output channels); natural channel order.
 template <int JB>
 __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, int n_jb) {
-    const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int g = blockIdx.y / n_jb, jb = blockIdx.y % n_jb;
-    if (o >= a.n_out) return;
+    if (pos >= a.n_out) return;
+    // a row order only reaches this kernel with the shapes of the natural-order matrix path (knob 15): thread = position, and a
+    // row-major table beside it holds its rows in position order (conv_common.h)
+    const int64_t o = a.row_order ? (int64_t)a.row_order[pos] : pos;
+    const int64_t trow = (a.row_order && table_is_row_major(a)) ? pos : o;
     const int64_t dst = a.out_map ? (int64_t)a.out_map[o * a.om_os + g * a.om_gs] : o * a.groups + g;
     if (dst < 0) return;
     const int c_in = a.c1 + a.c2;
@@ -260,7 +268,7 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, int n_jb) {
         int32_t idx[27];
         float xv[27];
 #pragma unroll
-        for (int k = 0; k < 27; ++k) idx[k] = a.nbr[(int64_t)k * a.nbr_ks + o * a.nbr_os];
+        for (int k = 0; k < 27; ++k) idx[k] = a.nbr[(int64_t)k * a.nbr_ks + trow * a.nbr_os];
 #pragma unroll
         for (int k = 0; k < 27; ++k) xv[k] = a.x1[(int64_t)(idx[k] >= 0 ? idx[k] : 0) * a.ld1];
 #pragma unroll
@@ -272,7 +280,7 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, int n_jb) {
         }
     } else
     for (int k = 0; k < a.n_off; ++k) {
-        const int32_t idx = a.nbr ? a.nbr[(int64_t)k * a.nbr_ks + o * a.nbr_os] : (int32_t)o;
+        const int32_t idx = a.nbr ? a.nbr[(int64_t)k * a.nbr_ks + trow * a.nbr_os] : (int32_t)o;
         if (idx < 0) continue;
         const float *xr1 = a.x1 + (int64_t)idx * a.ld1;
         const float *wk = wg + (int64_t)k * c_in * a.c_out + j0;
@@ -327,6 +335,16 @@ __global__ __launch_bounds__(256) void k_conv_valu(ConvArgs a, int n_jb) {
 // over the workgroup-tiled kernel: no barrier skew between waves whose 32-row blocks have different offsets, no
 // LDS round trip of W, work units of 1/2 .. 1/8 the size (shorter tail of a launch), and with NBW = 4 every gathered row is
 // fetched once instead of twice.  Same summation order (order 1).
+// A piece of a group of 8 channels, gathered as lane (i, h) = channels 4 h .. 4 h + 3 of row i, rearranged for the NATURAL chain: two
+// half exchanges (v_permlane32_swap: lanes 32-63 of the first operand trade places with lanes 0-31 of the second) leave
+//   .x = channels (0 | 1), .y = (2 | 3), .z = (4 | 5), .w = (6 | 7)        (low half-wave | high half-wave)
+// i.e. the MFMA that takes component j accumulates channel 2 j (k = 0) and then channel 2 j + 1 (k = 1).
+__device__ __forceinline__ f32x4 natural_pairs(const f32x4 a) {
+    const auto s0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.x), __float_as_uint(a.y), false, false);
+    const auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a.z), __float_as_uint(a.w), false, false);
+    return f32x4{__uint_as_float(s0[0]), __uint_as_float(s1[0]), __uint_as_float(s0[1]), __uint_as_float(s1[1])};
+}
+
 template <int NBW, int CH>
 struct WaveCfg {
     static constexpr int G8 = CH / 8;
@@ -358,8 +376,13 @@ struct WaveCfg {
 // of the launch order instead of one, and requests the NEXT unit's table rows and output rows while it computes the current one: on a
 // loaded chip the prologue's dependent loads (row order -> table rows -> gather addresses) took a wave 20-70 K cycles and its stores
 // 20-40 K, a fifth of its life in which it feeds no MFMA (profiles/r04/prologue_epilogue.md).  Same chains, same bits.
-template <int NBW, int CH, int SB, bool STAMPS = false, int OG = 1, bool FOLD = false, bool PERSIST = false>
-__global__ __launch_bounds__(256, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>::MIN_WAVES)) void k_conv_wave(ConvArgs a, const float *__restrict__ wp,
+// NAT (summation order 0 on the matrix pipe; C_out = 256, wp = the natural-order image of fpcc_conv_pack_weights_nat_f32): the same
+// gather, but before the MFMAs of a group of 8 channels the two half-waves exchange halves of the A piece (two v_permlane32_swap):
+// lane (i, h) then holds channels 2 j + h of the group for j = 0 .. 3 instead of 4 h + j, and the four MFMAs of the group -- each
+// accumulates k = 0 (low half-wave) then k = 1 (high half-wave) -- take the channels in ascending order: the natural chain of
+// k_conv_valu, bit for bit (an absent neighbour enters as fma(0, w, acc) == acc for finite w: the chain starts from +0 and is never -0).
+template <int NBW, int CH, int SB, bool STAMPS = false, int OG = 1, bool FOLD = false, bool PERSIST = false, bool NAT = false>
+__global__ __launch_bounds__(256, ((FOLD || PERSIST || NAT) ? 3 : WaveCfg<NBW, CH>::MIN_WAVES)) void k_conv_wave(ConvArgs a, const float *__restrict__ wp,
                                                                                                            int nbt, unsigned n_units,
                                                                                                            unsigned *unit_counter = nullptr) {
     constexpr int G8 = CH / 8;
@@ -593,7 +616,7 @@ __global__ __launch_bounds__(256, ((FOLD || PERSIST) ? 3 : WaveCfg<NBW, CH>::MIN
             __builtin_amdgcn_sched_barrier(SB);
 #pragma unroll
             for (int g8 = 0; g8 < G8; ++g8) {
-                const f32x4 av = ra[g8];
+                const f32x4 av = NAT ? natural_pairs(ra[g8]) : ra[g8];
 #pragma unroll
                 for (int nb = 0; nb < NBW; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, rb[g8][nb].x, acc[nb], 0, 0, 0);
 #pragma unroll
@@ -1109,6 +1132,25 @@ __global__ __launch_bounds__(256) void k_pack_weights(const float *__restrict__ 
     wp[e] = w[m * per_mat + (int64_t)(32 * cc + 8 * g8 + 4 * h + j) * c_out + 32 * nb + i];
 }
 
+// the natural-order image (k_conv_wave<..., NAT>): [m][cc][g8][nb][h][i][j] <- w[m][32 cc + 8 g8 + 2 j + h][32 nb + i] -- a lane's 16-byte
+// piece is j = 0 .. 3 of its half h, in MFMA issue order
+__global__ __launch_bounds__(256) void k_pack_weights_nat(const float *__restrict__ w, int64_t n_mats, int c_in, int c_out,
+                                                          float *__restrict__ wp) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t per_mat = (int64_t)c_in * c_out;
+    if (e >= n_mats * per_mat) return;
+    const int nbt = c_out / 32;
+    const int64_t m = e / per_mat;
+    int64_t r = e - m * per_mat;
+    const int j = (int)(r & 3); r >>= 2;
+    const int i = (int)(r & 31); r >>= 5;
+    const int h = (int)(r & 1); r >>= 1;
+    const int nb = (int)(r % nbt); r /= nbt;
+    const int g8 = (int)(r & 3); r >>= 2;
+    const int cc = (int)r;
+    wp[e] = w[m * per_mat + (int64_t)(32 * cc + 8 * g8 + 2 * j + h) * c_out + 32 * nb + i];
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // 0: VALU kernel, 16 / 32: MFMA kernel with that chunk size
@@ -1118,6 +1160,13 @@ int mfma_chunk(int c1, int c2, int c_out) {
     if (c_in % 32 == 0 && c1 % 32 == 0) return 32;
     if (c_in % 16 == 0 && c1 % 16 == 0) return 16;
     return 0;
+}
+
+// Shapes of the natural-order matrix path (k_conv_wave<..., NAT>): order 0 like every shape mfma_chunk() refuses, but evaluated on
+// v_mfma_f32_32x32x2_f32 -- the 256-wide layers of the expanded rate points
+bool natural_shape(int c1, int c2, int c_out, int n_offsets, int groups) {
+    return c_out == 256 && c1 >= 32 && c1 % 32 == 0 && c2 >= 0 && c2 % 32 == 0 && c1 + c2 <= 512 && n_offsets >= 1 && n_offsets <= kMaxOffsets &&
+           (groups == 1 || groups == 8);
 }
 
 int knob(int k);
@@ -1137,15 +1186,16 @@ int launch_mfma_cfg(ConvArgs a, hipStream_t s) {
 // kKnobStamps (0 | 16: the stamped builds of the grouped and the LDS-operand kernel, same bits) has no environment variable either.
 enum { kKnobWaveOn = 0, kKnobWaveNbw = 1, kKnobWaveSb = 2, kKnobStamps = 3, kKnobGroupedFoldRows = 4, kKnobMfmaCfg = 5, kKnobPointwiseRows = 6,
        kKnobGroupedOff = 7, kKnobGroupedNbw = 8, kKnobWave22Rows = 9, kKnobLdsRows = 10, kKnobLdsRowBlocks = 11, kKnobPersist = 12, kKnobFold64 = 13, kKnobK2s2tSparse = 14,
-       kKnobCount = 15 };
-int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+       kKnobNaturalMfma = 15, kKnobCount = 16 };
+int g_knob[kKnobCount] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 int knob(int k) {
     if (g_knob[k] < 0) {
         static const char *names[kKnobCount] = {"FPCC_CONV_WAVE", "FPCC_WAVE_NBW", "FPCC_WAVE_SB", "", "FPCC_GROUPED_FOLD_ROWS",
                                                 "FPCC_MFMA_TILE", "FPCC_POINTWISE_MIN_ROWS", "", "FPCC_GROUPED_NBW",
                                                 "FPCC_WAVE22_MIN_ROWS", "FPCC_LDS_MIN_ROWS", "FPCC_LDS_ROW_BLOCKS",
-                                                "FPCC_CONV_PERSIST", "FPCC_CONV_FOLD64", "FPCC_K2S2T_SPARSE"};
-        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0, 0, 0};
+                                                "FPCC_CONV_PERSIST", "FPCC_CONV_FOLD64", "FPCC_K2S2T_SPARSE",
+                                                "FPCC_CONV_NATURAL_MFMA"};
+        static const int defaults[kKnobCount] = {1, 0, 1, 0, 100 * 1024, 0, 32 * 1024, 0, 0, 0, 0, 2, 0, 0, 0, 2};
         const char *e = names[k][0] ? getenv(names[k]) : nullptr;
         g_knob[k] = e ? atoi(e) : defaults[k];
     }
@@ -1357,6 +1407,36 @@ int launch_wave(const ConvArgs &a, const float *wp, hipStream_t s) {
     return launch_wave_cfg<1>(a, wp, nbt, s);
 }
 
+
+// Natural-order matrix path (summation order 0; natural_shape()): knob 15 / FPCC_CONV_NATURAL_MFMA = 0: these shapes on k_conv_valu,
+// 1: on k_conv_wave<..., NAT>, 2 (default): on the matrix kernel from kNaturalMfmaRows output rows (rows x groups), k_conv_valu below.
+// Result-neutral: both kernels evaluate the same chain.  Threshold and unit widths: profiles/r09/expanded.md.
+constexpr int64_t kNaturalMfmaRows = 0;
+std::atomic<long long> g_natural_launches{0};
+inline bool use_natural_mfma(int64_t work) {
+    const int v = knob(kKnobNaturalMfma);
+    return v == 1 || (v >= 2 && work >= kNaturalMfmaRows);
+}
+
+template <int NBW>
+int launch_natural_cfg(const ConvArgs &a, const float *wp, hipStream_t s) {
+    constexpr int nbt = 8;
+    const int64_t units = ((a.n_out + 31) / 32) * (nbt / NBW);
+    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
+    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, false, false, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a,
+                       wp, nbt, (unsigned)units);
+    g_natural_launches.fetch_add(1, std::memory_order_relaxed);
+    return check_hip(hipGetLastError(), "k_conv_wave(natural)");
+}
+
+// unit width as for the order-1 wave kernel (launch_wave): two column blocks per wave from 32 Ki rows, one below; knob 1 forces 1 | 2
+// (four-block units are not built: beside the exchanged A pieces their 64 accumulator and 64 operand registers spill at three
+// waves per SIMD, and on the order-1 kernel they were never the fastest)
+int launch_natural(const ConvArgs &a, const float *wp, hipStream_t s) {
+    int nbw = knob(kKnobWaveNbw);
+    if (nbw <= 0) nbw = a.n_out * a.groups >= 32 * 1024 ? 2 : 1;
+    return nbw >= 2 ? launch_natural_cfg<2>(a, wp, s) : launch_natural_cfg<1>(a, wp, s);
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Per-point layers (ONE kernel offset, identity row map: MinkowskiLinear, 1x1x1 convolutions) on large maps.  In k_conv_wave
@@ -1617,7 +1697,17 @@ static bool use_grouped(int c1, int c2, int c_out, int n_offsets, int groups) {
 
 extern "C" int fpcc_conv_f32_order(int c1, int c2, int c_out) { return mfma_chunk(c1, c2, c_out) ? 1 : 0; }
 
+extern "C" int fpcc_conv_f32_natural_matrix(int c1, int c2, int c_out, int n_offsets, int groups) {
+    return natural_shape(c1, c2, c_out, n_offsets, groups) ? 1 : 0;
+}
+
+extern "C" int fpcc_conv_natural_use_matrix(int64_t rows) { return use_natural_mfma(rows) ? 1 : 0; }
+
+extern "C" long long fpcc_conv_natural_launches(void) { return g_natural_launches.load(std::memory_order_relaxed); }
+
 extern "C" int64_t fpcc_conv_f32_ws_bytes(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out) {
+    // the natural-order matrix kernel reads packed weights too (its own layout): room to pack into when the caller has no copy
+    if (n_out > 0 && natural_shape(c1, c2, c_out, n_offsets, groups)) return (int64_t)groups * n_offsets * (c1 + c2) * c_out * 4;
     // grouped shapes run on the wave kernel, which reads packed weights: without a packed copy from the caller they are packed
     // into the workspace on every call
     if (n_out > 0 && use_grouped(c1, c2, c_out, n_offsets, groups)) return (int64_t)n_offsets * (c1 + c2) * c_out * 4;
@@ -1681,6 +1771,21 @@ extern "C" int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offs
     return (int64_t)groups * n_offsets * (c1 + c2) * c_out;
 }
 
+extern "C" int64_t fpcc_conv_packed_floats_nat(int c1, int c2, int c_out, int n_offsets, int groups) {
+    if (!natural_shape(c1, c2, c_out, n_offsets, groups)) return 0;
+    return (int64_t)groups * n_offsets * (c1 + c2) * c_out;
+}
+
+extern "C" int fpcc_conv_pack_weights_nat_f32(const float *w, int64_t n_mats, int c_in, int c_out, float *w_packed, void *stream) {
+    if (n_mats < 0 || c_in < 32 || c_in % 32 || c_in > 512 || c_out != 256)
+        return fail_arg("conv_pack_weights_nat: c_in must be a multiple of 32 (<= 512) and c_out 256");
+    if (n_mats == 0) return FPCC_OK;
+    if (!w || !w_packed) return fail_arg("conv_pack_weights_nat: null pointer");
+    hipLaunchKernelGGL(k_pack_weights_nat, dim3(blocks_for(n_mats * c_in * c_out, 256)), dim3(256), 0, as_stream(stream), w, n_mats,
+                       c_in, c_out, w_packed);
+    return check_hip(hipGetLastError(), "k_pack_weights_nat");
+}
+
 extern "C" int fpcc_conv_pack_weights_f32(const float *w, int64_t n_mats, int c_in, int c_out, float *w_packed, void *stream) {
     if (n_mats < 0 || c_in < 32 || c_in % 32 || (c_out != 32 && c_out != 64 && c_out != 128))
         return fail_arg("conv_pack_weights: c_in must be a multiple of 32 and c_out one of 32, 64, 128");
@@ -1735,7 +1840,26 @@ extern "C" int fpcc_conv_f32_pk(const float *x1, int c1, int ld1, const float *x
                out_map, om_os, om_gs, out, ldo, n_out, act, slope, clip, row_order};
     hipStream_t s = as_stream(stream);
     int ch = mfma_chunk(c1, c2, c_out);
-    if (row_order && !ch) return fail_arg("conv_f32: row_order is a feature of the MFMA path (fpcc_conv_f32_order() != 0)");
+    // "runs on the matrix pipe" and "summation order != 0" are two notions: the natural-order shapes are order 0 on the matrix pipe
+    const bool nat = natural_shape(c1, c2, c_out, n_offsets, groups);
+    if (row_order && !ch && !nat)
+        return fail_arg("conv_f32: row_order is a feature of the matrix path (fpcc_conv_f32_order() != 0 or fpcc_conv_f32_natural_matrix())");
+    // The matrix kernel needs what the VALU kernel never asked of these shapes: 16-byte aligned rows, and packed weights or a workspace
+    // to pack into.  A call without them is served as it always was, by k_conv_valu -- the same chain, the same bits.
+    const bool nat_operands = aligned16(x1) && ld1 % 4 == 0 && (c2 == 0 || (aligned16(x2) && ld2 % 4 == 0)) &&
+                              (w_packed ? aligned16(w_packed)
+                                        : (ws && aligned16(ws) && ws_bytes >= (int64_t)groups * n_offsets * (c1 + c2) * c_out * 4));
+    if (nat && nat_operands && use_natural_mfma(n_out * (int64_t)groups)) {
+        // PRECONDITION (as for fpcc_conv_ones_k3_f32): finite weights.  An absent neighbour enters the chain as fma(0, w, acc), which
+        // is acc for finite w (the chain starts from +0 and a sum that cancels is +0, so acc is never -0) where k_conv_valu skips it;
+        // with an infinite or NaN weight the two differ.
+        const float *wp = w_packed;
+        if (!wp) {
+            if (int rc = fpcc_conv_pack_weights_nat_f32(w, (int64_t)groups * n_offsets, c1 + c2, c_out, static_cast<float *>(ws), stream)) return rc;
+            wp = static_cast<const float *>(ws);
+        }
+        return launch_natural(a, wp, s);
+    }
     if (ch && n_offsets > kMaxOffsets) return fail_arg("conv_f32: the MFMA path supports at most 27 kernel offsets");
     if (ch && !(aligned16(x1) && ld1 % 4 == 0 && aligned16(w) && (c2 == 0 || (aligned16(x2) && ld2 % 4 == 0))))
         return fail_arg("conv_f32: the MFMA path needs 16-byte aligned inputs and row strides that are multiples of 4");

@@ -942,6 +942,10 @@ class _ConvBase(nn.Module):
                 wp, bp = self._padded_weights(x1.shape[1], 0 if x2 is None else x2.shape[1], plan)
                 out = ops.conv_f32(self._pad_cols(x1, plan[0]), wp, plan[2], src.n, x2=self._pad_cols(x2, plan[1]), bias=bp,
                                    act=act.kind, slope=act.slope, clip=clip, pack=True)[:, :c_out]
+                if c_out < 8:
+                    # as in the 3x3x3 branch below: a narrow head (the 32 -> 1 classify layer of a two- or three-stage decoder on a
+                    # map of PAD_MIN_ROWS rows or more) is read as a flat vector by the top-k pruning, which needs it contiguous
+                    out = out.contiguous()
             else:
                 out = ops.conv_f32(x1, w, c_out, src.n, **kw)
         elif self.ks == 3:
@@ -974,7 +978,10 @@ class _ConvBase(nn.Module):
                 # finest level is then never built
                 out = ops.conv_ones_k3(cm._mask27(src), w, c_out, bias=kw['bias'], act=act.kind, slope=act.slope, clip=clip)
             else:
-                mfma = ops.conv_order(x1.shape[1], 0 if x2 is None else x2.shape[1], c_out) != 0
+                # on the matrix pipe: an MFMA summation order, or order 0 on the natural-order matrix kernel (256-wide layers) -- either
+                # takes a row order and the row-major table in position order
+                c2 = 0 if x2 is None else x2.shape[1]
+                mfma = ops.conv_order(x1.shape[1], c2, c_out) != 0 or ops.conv_natural_matrix(x1.shape[1], c2, c_out, 27, 1)
                 # 16 input channels: one 64-byte gather per neighbour -- Morton locality beats block skipping
                 ro = cm._row_order(src) if mfma and x1.shape[1] + (0 if x2 is None else x2.shape[1]) > 16 else None
                 out = ops.conv_f32(x1, w, c_out, src.n, **cm._k3_table(src, mfma and kw.get('pack', False) is True, ro), row_order=ro, **kw)
@@ -985,8 +992,10 @@ class _ConvBase(nn.Module):
             c_in = x1.shape[1] + (0 if x2 is None else x2.shape[1])
             # (16 input channels: the one such layer -- 16 -> 64 onto the stride-2 map -- gains 0.19 ms per batch in pattern order and its
             # order costs more than that to build: measured, left in Morton order)
-            if kw.get('pack', False) is True and c_in > 16 and ops.conv_order(x1.shape[1], 0 if x2 is None else x2.shape[1], c_out, 8, 1, dst.n) != 0:
-                ro, table = cm._k2_order(src)              # grouped MFMA shapes: parents in child-pattern order on large maps
+            c2 = 0 if x2 is None else x2.shape[1]
+            if kw.get('pack', False) is True and c_in > 16 and (ops.conv_order(x1.shape[1], c2, c_out, 8, 1, dst.n) != 0 or
+                                                                  ops.conv_natural_matrix(x1.shape[1], c2, c_out, 8, 1)):
+                ro, table = cm._k2_order(src)              # shapes of the matrix pipe: parents in child-pattern order on large maps
             else:
                 ro, table = None, src.child_row
             out = ops.conv_f32(x1, w, c_out, dst.n, nbr=table, n_offsets=8, nbr_ks=1, nbr_os=8, row_order=ro, **kw)

@@ -54,6 +54,11 @@ _SIGS = {
     'fpcc_numerics_version': (_i32, []),
     'fpcc_conv_packed_floats': (_i64, [_i32, _i32, _i32, _i32, _i32]),
     'fpcc_conv_pack_weights_f32': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    'fpcc_conv_f32_natural_matrix': (_i32, [_i32, _i32, _i32, _i32, _i32]),
+    'fpcc_conv_packed_floats_nat': (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    'fpcc_conv_pack_weights_nat_f32': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),
+    'fpcc_conv_natural_launches': (_i64, []),
+    'fpcc_conv_natural_use_matrix': (_i32, [_i64]),
     'fpcc_nn_dist2': (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp]),
     'fpcc_knn3d': (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp]),
     'fpcc_sum_i64': (_i32, [_vp, _i64, _vp, _vp]),
@@ -493,13 +498,19 @@ _PACKED_MAX = 1024
 
 
 def packed_weights(w: torch.Tensor, c1: int, c2: int, c_out: int, n_offsets: int, groups: int, fresh: bool = False) -> Optional[torch.Tensor]:
-    """packed copy of w [groups, n_offsets, c1 + c2, c_out] for fpcc_conv_f32_pk, or None when the shape has no wave kernel.
+    """packed copy of w [groups, n_offsets, c1 + c2, c_out] for fpcc_conv_f32_pk, or None when the shape has no wave kernel: the
+    order-1 image (fpcc_conv_pack_weights_f32), or for the shapes of the natural-order matrix path (conv_natural_matrix) the
+    natural-order image (fpcc_conv_pack_weights_nat_f32) -- a shape has one or the other, never both.
     fresh: pack now and do not cache (weights that change every step: training)"""
-    if not lib().fpcc_conv_packed_floats(c1, c2, c_out, n_offsets, groups):
+    if lib().fpcc_conv_packed_floats(c1, c2, c_out, n_offsets, groups):
+        pack_fn = lib().fpcc_conv_pack_weights_f32
+    elif c_out == 256 and lib().fpcc_conv_packed_floats_nat(c1, c2, c_out, n_offsets, groups):
+        pack_fn = lib().fpcc_conv_pack_weights_nat_f32
+    else:
         return None
     if fresh:
         out = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
-        _ok(lib().fpcc_conv_pack_weights_f32(w.data_ptr(), groups * n_offsets, c1 + c2, c_out, out.data_ptr(), _stream()))
+        _ok(pack_fn(w.data_ptr(), groups * n_offsets, c1 + c2, c_out, out.data_ptr(), _stream()))
         return out
     key = (w.data_ptr(), w.numel(), c1 + c2, c_out)
     ent = _PACKED.get(key)
@@ -507,7 +518,7 @@ def packed_weights(w: torch.Tensor, c1: int, c2: int, c_out: int, n_offsets: int
         _PACKED.move_to_end(key)
         return ent[2]
     out = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
-    _ok(lib().fpcc_conv_pack_weights_f32(w.data_ptr(), groups * n_offsets, c1 + c2, c_out, out.data_ptr(), _stream()))
+    _ok(pack_fn(w.data_ptr(), groups * n_offsets, c1 + c2, c_out, out.data_ptr(), _stream()))
     _PACKED[key] = (w, w._version, out)
     while len(_PACKED) > _PACKED_MAX:
         _PACKED.popitem(last=False)
@@ -521,12 +532,18 @@ KNOB_GROUPED_OFF, KNOB_GROUPED_NBW, KNOB_WAVE22_ROWS = 7, 8, 9      # 7: experim
 KNOB_PERSIST = 12     # workgroups per CU of the persistent grouped / folded kernels (0 = off)
 KNOB_FOLD64 = 13      # folded launches on 64 x 64 wave units: 0 = large maps with a row order, 1 = never, 2 = every folded launch
 KNOB_K2S2T_SPARSE = 14  # transposed 2x2x2 convolution over the existing children: 0 = from a child-row threshold, 1 = never, 2 = always
+KNOB_NATURAL_MFMA = 15  # shapes of conv_natural_matrix (order 0, C_out = 256): 0 = VALU kernel, 1 = natural-order matrix kernel, 2 = by a row threshold (default)
 KNOB_LDS_ROWS, KNOB_LDS_ROW_BLOCKS = 10, 11  # rows from which order-3 layers take both operands through LDS (0 = never); row blocks per workgroup (2 | 3 | 4)
 
 
 def conv_fold64_launches() -> int:
     """launches of the folded 64 x 64 wave unit (k_conv_fold64) by this process so far"""
     return int(lib().fpcc_conv_fold64_launches())
+
+
+def conv_natural_launches() -> int:
+    """launches of the natural-order matrix kernel (order 0 on MFMA: conv_natural_matrix shapes) by this process so far"""
+    return int(lib().fpcc_conv_natural_launches())
 
 
 def numerics_version() -> int:
@@ -678,7 +695,8 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
         om_os = groups
     ws, ws_bytes = None, 0
     wp = packed_weights(w, c1, c2, c_out, n_offsets, groups, fresh=(pack == 'fresh')) if pack else None
-    if wp is None and nbr is not None and n_offsets >= 8:      # a grouped (order 3) shape without a packed copy: room to pack into
+    # a grouped (order 3) shape or one of the natural-order matrix path without a packed copy: room to pack into
+    if wp is None and ((nbr is not None and n_offsets >= 8) or c_out == 256):
         ws_bytes = lib().fpcc_conv_f32_ws_bytes(c1, c2, c_out, n_offsets, groups, n_out)
         if ws_bytes:
             ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x1.device)
@@ -696,7 +714,10 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
     if trace is None:
         _untraced_launch(fn, call)
         return out
-    _traced_launch(trace, fn, call, {'mfma': bool(conv_order(c1, c2, c_out, n_offsets, groups, n_out)), 'c_in': c1 + c2, 'c_out': c_out,
+    # 'mfma': whether the launch runs on the matrix pipe -- a summation order other than 0, or order 0 on the natural-order matrix kernel
+    on_matrix = bool(conv_order(c1, c2, c_out, n_offsets, groups, n_out)) or \
+        (conv_natural_matrix(c1, c2, c_out, n_offsets, groups) and conv_natural_uses_matrix(n_out * groups))
+    _traced_launch(trace, fn, call, {'mfma': on_matrix, 'c_in': c1 + c2, 'c_out': c_out,
                                      'n_out': n_out, 'groups': groups, 'n_offsets': n_offsets, 'nbr': nbr,
                                      'nbr_ks': nbr_ks, 'nbr_os': nbr_os})
     return out
@@ -1199,6 +1220,8 @@ def table_conv_chunk(c_in: int, c_out: int, k: int) -> int:
     and up to 27 on the MFMA path: shapes of the VALU path keep the partition into 32s they always had (their fp32 bits are pinned
     by fixtures), MFMA-capable shapes with more than 27 offsets go in 16s.  ONE rule for the inference partition
     (int_sparse_conv.Conv3d._run) and the training partition (autograd._forward), so that both sum in the same order."""
+    # the ORDER decides here, not where the launch runs: order-0 shapes keep their partition into 32s also where their launches of
+    # <= 27 offsets would go to the natural-order matrix kernel (conv_natural_matrix) -- launches of 32 offsets stay on the VALU kernel
     mfma = conv_order(c_in, 0, c_out, 1, 1, 0) != 0
     if not mfma:
         return 32
@@ -1208,6 +1231,19 @@ def table_conv_chunk(c_in: int, c_out: int, k: int) -> int:
 @functools.lru_cache(maxsize=8192)
 def conv_order(c1: int, c2: int, c_out: int, n_offsets: int = 1, groups: int = 1, n_out: int = 0) -> int:
     return lib().fpcc_conv_f32_order_ex(c1, c2, c_out, n_offsets, groups, n_out)
+
+
+@functools.lru_cache(maxsize=8192)
+def conv_natural_matrix(c1: int, c2: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
+    """whether the shape belongs to the natural-order matrix path (fpcc_conv_f32_natural_matrix): summation order 0 -- conv_order()
+    stays 0 -- evaluated on MFMA; such a shape takes a row order and a packed (natural-order) weight image like the order-1 shapes"""
+    return bool(lib().fpcc_conv_f32_natural_matrix(c1, c2, c_out, n_offsets, groups))
+
+
+def conv_natural_uses_matrix(rows: int) -> bool:
+    """whether knob 15 (KNOB_NATURAL_MFMA) sends a conv_natural_matrix shape with `rows` output rows x groups to the matrix kernel
+    (fpcc_conv_natural_use_matrix; the VALU kernel otherwise -- same bits)"""
+    return bool(lib().fpcc_conv_natural_use_matrix(int(rows)))
 
 
 def gather_sum(y: torch.Tensor, nbr: torch.Tensor, n_offsets: int, nbr_ks: int, nbr_os: int, n: int, *,

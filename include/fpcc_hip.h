@@ -151,7 +151,10 @@ enum { FPCC_ACT_NONE = 0, FPCC_ACT_PRELU = 1, FPCC_ACT_RELU = 2 };
  *                                            the offsets present, the partial sums are added as ((g0 + g1) + g2) + g3, then bias
  *     order 1 (MFMA chain)                   every other MFMA shape: one chain, offsets ascending, 0,4,1,5,2,6,3,7 inside
  *                                            aligned groups of 8 channels
- *     order 0 (natural chain)                shapes outside the MFMA path
+ *     order 0 (natural chain)                every other shape: one chain from +0, offsets ascending, channels ascending inside an
+ *                                            offset, bias last.  Evaluated by the VALU kernel -- or, for the shapes of
+ *                                            fpcc_conv_f32_natural_matrix() (C_out = 256: the expanded rate points), on the matrix
+ *                                            pipe in that same order; which of the two runs is a tuning matter (knob 15), not an order
  *     zero-padding to an MFMA shape          per-point / 3x3x3 layers on maps of at least FPCC_PAD_MIN_ROWS rows
  *     two-phase conv3 -> 1 channel (order 2) every 3x3x3 layer with one output channel and C_in % 16 == 0: per offset its own
  *                                            chain, offsets' sums added in ascending order
@@ -190,7 +193,9 @@ int fpcc_numerics_version(void);
  *
  * Summation order (fixed, documented for bit-exact checking): see "Numerics version" above; fpcc_conv_f32_order_ex() reports
  * the order of a shape (0 natural chain, 1 MFMA chain, 3 grouped).  A grouped shape runs on the wave kernel and needs packed
- * weights: from the caller (fpcc_conv_f32_pk), or packed per call into a workspace of fpcc_conv_f32_ws_bytes() bytes.
+ * weights: from the caller (fpcc_conv_f32_pk), or packed per call into a workspace of fpcc_conv_f32_ws_bytes() bytes; so does a
+ * shape of the natural-order matrix path (below), with its own packed layout.
+ * row_order (NULL: identity) is taken by every shape of the matrix pipe: fpcc_conv_f32_order() != 0 or fpcc_conv_f32_natural_matrix().
  */
 int fpcc_conv_f32(const float *x1, int c1, int ld1, const float *x2, int c2, int ld2,
                   const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
@@ -207,6 +212,27 @@ int fpcc_conv_f32(const float *x1, int c1, int ld1, const float *x2, int c2, int
  *     w_packed[m][cc][g8][nb][h][i][j] = w[m][32 cc + 8 g8 + 4 h + j][32 nb + i]      (same number of floats);
  * the caller caches it next to the weights (fastpcc_amd/hipops.py keeps one per weight tensor). */
 int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int groups);
+/* Natural-order matrix path: summation order 0 on v_mfma_f32_32x32x2_f32.  fpcc_conv_f32_natural_matrix() is 1 for the shapes it takes:
+ *     C_out = 256;  c1, c2 multiples of 32 (c1 >= 32, c2 >= 0) with c1 + c2 <= 512;  1 <= n_offsets <= 27;  groups 1 or 8
+ * -- the 256-wide layers of the expanded rate points (config/convolutional/lossy_coord_v2/expanded_r3.yaml ... expanded_r6.yaml).
+ * fpcc_conv_f32_order() / _order_ex() stay 0 for them: "on the matrix pipe" and "order != 0" are two notions.  The kernel is the
+ * wave-autonomous one; after gathering a group of 8 channels the two half-waves exchange halves of their 16-byte A pieces (two
+ * v_permlane32_swap), so that the group's four MFMAs take the channels in ascending order: every output element is the chain the
+ * VALU kernel evaluates, bit for bit, and knob 15 only chooses between the two kernels.
+ * PRECONDITION: finite weights.  An absent neighbour enters the chain as fma(0, w, acc) where the VALU kernel skips it; for finite w
+ * that is acc (the chain starts from +0 and is never -0).
+ * fpcc_conv_pack_weights_nat_f32: w [n_mats][c_in][256] (n_mats = groups * n_offsets; c_in a multiple of 32, <= 512) ->
+ *     w_packed[m][cc][g8][nb][h][i][j] = w[m][32 cc + 8 g8 + 2 j + h][32 nb + i]      (same number of floats)
+ * -- the image fpcc_conv_f32_pk expects as `w_packed` for these shapes (fpcc_conv_packed_floats_nat() floats, 0 for any other
+ * shape; without it the weights are packed per call into the workspace: same bits).  A call that brings neither a packed image nor
+ * a workspace of fpcc_conv_f32_ws_bytes() bytes, or whose rows are not 16-byte aligned (ld % 4), runs on the VALU kernel as before.
+ * fpcc_conv_natural_use_matrix: 1 when knob 15 sends such a shape with `rows` output rows x groups to the matrix kernel, else 0.
+ * fpcc_conv_natural_launches: diagnostics, launches of the natural-order matrix kernel by this process so far (tests). */
+int fpcc_conv_f32_natural_matrix(int c1, int c2, int c_out, int n_offsets, int groups);
+int64_t fpcc_conv_packed_floats_nat(int c1, int c2, int c_out, int n_offsets, int groups);
+int fpcc_conv_pack_weights_nat_f32(const float *w, int64_t n_mats, int c_in, int c_out, float *w_packed, void *stream);
+int fpcc_conv_natural_use_matrix(int64_t rows);
+long long fpcc_conv_natural_launches(void);
 /* Tuning knobs of the wave kernel (process-wide; initial values from FPCC_CONV_WAVE / FPCC_WAVE_NBW / FPCC_WAVE_SB).  None
  * changes a result (knob 7 apart, see there) -- the tests run every setting against the same oracle output.  Returns the previous value.
  *   0  use the wave kernel when packed weights are given (1) or the workgroup-tiled kernel (0)
@@ -235,7 +261,10 @@ int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int gr
  *      units on every such launch.  The persistent form (knob 12) keeps its 32-row units.  Same order 3, same bits.
  *  14  transposed 2x2x2 stride-2 convolution onto an existing child map (FPCC_K2S2T_SPARSE), as answered by
  *      fpcc_conv_k2s2t_use_sparse: 0 = over the existing children (fpcc_conv_k2s2t_f32) from 204800 child rows upwards,
- *      the groups = 8 / out_map form of fpcc_conv_f32 below; 1 = never; 2 = for every shape the new form covers.  Same bits. */
+ *      the groups = 8 / out_map form of fpcc_conv_f32 below; 1 = never; 2 = for every shape the new form covers.  Same bits.
+ *  15  shapes of fpcc_conv_f32_natural_matrix() (FPCC_CONV_NATURAL_MFMA): 0 = on the VALU kernel, 1 = on the natural-order matrix
+ *      kernel, 2 (default) = on the matrix kernel from a row threshold (rows x groups; 0 rows as measured: profiles/r09/expanded.md),
+ *      the VALU kernel below it.  Same order 0, same bits. */
 int fpcc_conv_set_tuning(int which, int value);
 /* Diagnostics: launches of k_conv_fold64 by this process so far (tests check which unit a forced launch took). */
 long long fpcc_conv_fold64_launches(void);
