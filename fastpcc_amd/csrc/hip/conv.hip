@@ -1689,36 +1689,53 @@ int launch_valu(const ConvArgs &a, hipStream_t s) {
 
 using namespace fpcc;
 
-// Which multi-offset shapes are evaluated grouped (summation order 3): a property of the shape alone -- not of the row count, the
-// caller's arguments or a tuning knob (knob 7 exists for A/B experiments under FPCC_EXPERIMENT=1).
-static bool use_grouped(int c1, int c2, int c_out, int n_offsets, int groups) {
-    return mfma_chunk(c1, c2, c_out) == 32 && n_offsets >= 8 && n_offsets <= kMaxOffsets && groups == 1 && !knob(kKnobGroupedOff);
+// THE classification of a convolution shape: everything below that asks where a shape runs, in which summation order, which packed
+// weight image it reads and how much room it packs into reads this plan (include/fpcc_hip.h: fpcc_conv_plan).  A function of the shape
+// and of knob 7 alone (experiments under FPCC_EXPERIMENT=1: multi-offset layers in order 1 instead of grouped) -- not of the row
+// count, the caller's arguments or any other knob; the one row-dependent question is use_natural_mfma(rows).
+static fpcc_conv_plan conv_plan(int c1, int c2, int c_out, int n_offsets, int groups) {
+    fpcc_conv_plan p{};
+    p.chunk = mfma_chunk(c1, c2, c_out);
+    const bool nat = natural_shape(c1, c2, c_out, n_offsets, groups);         // order 0 on the matrix pipe; never an mfma_chunk shape
+    const bool wave = p.chunk == 32 && n_offsets >= 1 && n_offsets <= kMaxOffsets && groups >= 1;    // shapes the wave kernel takes
+    const bool grouped = wave && n_offsets >= 8 && groups == 1 && !knob(kKnobGroupedOff);            // multi-offset: summation order 3
+    p.order = grouped ? 3 : p.chunk ? 1 : 0;
+    p.matrix = p.chunk || nat;
+    p.packed = nat ? 2 : wave ? 1 : 0;
+    p.packed_floats = p.packed ? (int64_t)groups * n_offsets * (c1 + c2) * c_out : 0;
+    // grouped and natural-order shapes run on packed weights only: a call that brings no image packs into a workspace
+    p.ws_bytes = grouped || nat ? 4 * p.packed_floats : 0;
+    return p;
 }
 
-extern "C" int fpcc_conv_f32_order(int c1, int c2, int c_out) { return mfma_chunk(c1, c2, c_out) ? 1 : 0; }
+extern "C" int fpcc_conv_f32_plan(int c1, int c2, int c_out, int n_offsets, int groups, fpcc_conv_plan *plan) {
+    if (!plan) return fail_arg("conv_f32_plan: null pointer");
+    *plan = conv_plan(c1, c2, c_out, n_offsets, groups);
+    return FPCC_OK;
+}
 
+// the six older shape queries: one field of the plan each
+extern "C" int fpcc_conv_f32_order(int c1, int c2, int c_out) { return conv_plan(c1, c2, c_out, 1, 1).order; }
+extern "C" int fpcc_conv_f32_order_ex(int c1, int c2, int c_out, int n_offsets, int groups, int64_t) {
+    return conv_plan(c1, c2, c_out, n_offsets, groups).order;
+}
 extern "C" int fpcc_conv_f32_natural_matrix(int c1, int c2, int c_out, int n_offsets, int groups) {
-    return natural_shape(c1, c2, c_out, n_offsets, groups) ? 1 : 0;
+    return conv_plan(c1, c2, c_out, n_offsets, groups).packed == 2;
+}
+extern "C" int64_t fpcc_conv_f32_ws_bytes(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out) {
+    return n_out > 0 ? conv_plan(c1, c2, c_out, n_offsets, groups).ws_bytes : 0;
+}
+static int64_t packed_floats_of(const fpcc_conv_plan &p, int image) { return p.packed == image ? p.packed_floats : 0; }
+extern "C" int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int groups) {
+    return packed_floats_of(conv_plan(c1, c2, c_out, n_offsets, groups), 1);
+}
+extern "C" int64_t fpcc_conv_packed_floats_nat(int c1, int c2, int c_out, int n_offsets, int groups) {
+    return packed_floats_of(conv_plan(c1, c2, c_out, n_offsets, groups), 2);
 }
 
 extern "C" int fpcc_conv_natural_use_matrix(int64_t rows) { return use_natural_mfma(rows) ? 1 : 0; }
 
 extern "C" long long fpcc_conv_natural_launches(void) { return g_natural_launches.load(std::memory_order_relaxed); }
-
-extern "C" int64_t fpcc_conv_f32_ws_bytes(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out) {
-    // the natural-order matrix kernel reads packed weights too (its own layout): room to pack into when the caller has no copy
-    if (n_out > 0 && natural_shape(c1, c2, c_out, n_offsets, groups)) return (int64_t)groups * n_offsets * (c1 + c2) * c_out * 4;
-    // grouped shapes run on the wave kernel, which reads packed weights: without a packed copy from the caller they are packed
-    // into the workspace on every call
-    if (n_out > 0 && use_grouped(c1, c2, c_out, n_offsets, groups)) return (int64_t)n_offsets * (c1 + c2) * c_out * 4;
-    return 0;
-}
-
-extern "C" int fpcc_conv_f32_order_ex(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out) {
-    (void)n_out;                                    // the order is a function of the shape alone (numerics version 2)
-    if (use_grouped(c1, c2, c_out, n_offsets, groups)) return 3;
-    return mfma_chunk(c1, c2, c_out) ? 1 : 0;
-}
 
 extern "C" int fpcc_numerics_version(void) { return FPCC_NUMERICS_VERSION; }
 
@@ -1763,17 +1780,6 @@ extern "C" int fpcc_conv_set_tuning(int which, int value) {
     const int before = knob(which);
     g_knob[which] = value < 0 ? 0 : value;
     return before;
-}
-
-extern "C" int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int groups) {
-    // the wave kernel takes the 32-channel-chunk shapes of the MFMA path
-    if (mfma_chunk(c1, c2, c_out) != 32 || n_offsets < 1 || n_offsets > kMaxOffsets || groups < 1) return 0;
-    return (int64_t)groups * n_offsets * (c1 + c2) * c_out;
-}
-
-extern "C" int64_t fpcc_conv_packed_floats_nat(int c1, int c2, int c_out, int n_offsets, int groups) {
-    if (!natural_shape(c1, c2, c_out, n_offsets, groups)) return 0;
-    return (int64_t)groups * n_offsets * (c1 + c2) * c_out;
 }
 
 extern "C" int fpcc_conv_pack_weights_nat_f32(const float *w, int64_t n_mats, int c_in, int c_out, float *w_packed, void *stream) {
@@ -1834,22 +1840,20 @@ extern "C" int fpcc_conv_f32_pk(const float *x1, int c1, int ld1, const float *x
     if (act != FPCC_ACT_NONE && act != FPCC_ACT_PRELU && act != FPCC_ACT_RELU) return fail_arg("conv_f32: unknown activation");
     if (act == FPCC_ACT_PRELU && !slope) return fail_arg("conv_f32: PReLU needs a slope pointer");
     if ((int64_t)groups * ((c_out + 15) / 16) > 65535) return fail_arg("conv_f32: too many groups");
-    if (n_out == 0) return FPCC_OK;
 
     ConvArgs a{x1, c1, ld1, x2, c2, ld2, nbr, n_offsets, nbr_ks, nbr_os, w, bias, c_out, groups,
                out_map, om_os, om_gs, out, ldo, n_out, act, slope, clip, row_order};
     hipStream_t s = as_stream(stream);
-    int ch = mfma_chunk(c1, c2, c_out);
     // "runs on the matrix pipe" and "summation order != 0" are two notions: the natural-order shapes are order 0 on the matrix pipe
-    const bool nat = natural_shape(c1, c2, c_out, n_offsets, groups);
-    if (row_order && !ch && !nat)
+    const fpcc_conv_plan plan = conv_plan(c1, c2, c_out, n_offsets, groups);
+    const int ch = plan.chunk;
+    if (row_order && !plan.matrix)
         return fail_arg("conv_f32: row_order is a feature of the matrix path (fpcc_conv_f32_order() != 0 or fpcc_conv_f32_natural_matrix())");
     // The matrix kernel needs what the VALU kernel never asked of these shapes: 16-byte aligned rows, and packed weights or a workspace
     // to pack into.  A call without them is served as it always was, by k_conv_valu -- the same chain, the same bits.
     const bool nat_operands = aligned16(x1) && ld1 % 4 == 0 && (c2 == 0 || (aligned16(x2) && ld2 % 4 == 0)) &&
-                              (w_packed ? aligned16(w_packed)
-                                        : (ws && aligned16(ws) && ws_bytes >= (int64_t)groups * n_offsets * (c1 + c2) * c_out * 4));
-    if (nat && nat_operands && use_natural_mfma(n_out * (int64_t)groups)) {
+                              (w_packed ? aligned16(w_packed) : (ws && aligned16(ws) && ws_bytes >= plan.ws_bytes));
+    if (plan.packed == 2 && nat_operands && use_natural_mfma(n_out * (int64_t)groups)) {
         // PRECONDITION (as for fpcc_conv_ones_k3_f32): finite weights.  An absent neighbour enters the chain as fma(0, w, acc), which
         // is acc for finite w (the chain starts from +0 and a sum that cancels is +0, so acc is never -0) where k_conv_valu skips it;
         // with an infinite or NaN weight the two differ.
@@ -1863,12 +1867,12 @@ extern "C" int fpcc_conv_f32_pk(const float *x1, int c1, int ld1, const float *x
     if (ch && n_offsets > kMaxOffsets) return fail_arg("conv_f32: the MFMA path supports at most 27 kernel offsets");
     if (ch && !(aligned16(x1) && ld1 % 4 == 0 && aligned16(w) && (c2 == 0 || (aligned16(x2) && ld2 % 4 == 0))))
         return fail_arg("conv_f32: the MFMA path needs 16-byte aligned inputs and row strides that are multiples of 4");
-    if (nbr && use_grouped(c1, c2, c_out, n_offsets, groups)) {
+    if (nbr && plan.order == 3) {
         // summation order 3, whatever the caller passed (the order is a property of the shape)
         if (out_map) return fail_arg("conv_f32: grouped shapes do not take an output map");
         const float *wp = w_packed;
         if (!wp) {
-            if (!ws || ws_bytes < fpcc_conv_f32_ws_bytes(c1, c2, c_out, n_offsets, groups, n_out) || !aligned16(ws))
+            if (!ws || ws_bytes < plan.ws_bytes || !aligned16(ws))
                 return fail_arg("conv_f32: this shape needs packed weights or a 16-byte aligned workspace of fpcc_conv_f32_ws_bytes() bytes");
             if (int rc = fpcc_conv_pack_weights_f32(w, n_offsets, c1 + c2, c_out, static_cast<float *>(ws), stream)) return rc;
             wp = static_cast<const float *>(ws);

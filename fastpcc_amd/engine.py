@@ -730,22 +730,33 @@ def _pad_plan(c1: int, c2: int, c_out: int, n_out: int):
     return c1p, c2p, c_outp
 
 
+def _layer_form(kind: str, c1: int, c2: int, c_out: int, rows: int):
+    """The form a layer takes and the shape it is evaluated at, -> (form, (c1, c2, c_out)) -- read by summation_order() (what the
+    tests hand to the oracle) and by _ConvBase._forward_fused (what runs):
+    'gen'    a generative layer's 8 octant kernels side by side in one dense GEMM (order 1).  ONE exception, as before this function
+             existed: only a GENERATIVE module keeps the side-by-side weights, so a transposed layer onto a generated map -- kind 'gen'
+             too -- runs as the plain groups = 8 launch in _forward_fused although this function and summation_order() say 'gen';
+    'split'  3x3x3 onto one channel: dot products per input row, then a gather (order 2);
+    'pad'    zero-padded to the MFMA shape returned (_pad_plan; order of that shape);
+    'plain'  the shape as it is.
+    kind: 'k1' | 'k3' | 'k2s2' | 'k2s2T' | 'gen'; rows: the row count PAD_MIN_ROWS is compared with (the map's, or its clouds')"""
+    if kind == 'gen' and c2 == 0 and _packed_gen_ok(c1, c_out):
+        return 'gen', (c1, c2, c_out)
+    if kind == 'k3' and _split_k3_ok(c1, c2, c_out):
+        return 'split', (c1, c2, c_out)
+    plan = _pad_plan(c1, c2, c_out, rows) if kind in ('k1', 'k3') else None
+    return ('plain', (c1, c2, c_out)) if plan is None else ('pad', plan)
+
+
 def summation_order(kind: str, c1: int, c2: int, c_out: int, n_out: int = 0) -> int:
     """Which documented fp32 summation order (include/fpcc_hip.h) a layer of this shape and size is evaluated in:
-    0 natural chain, 1 MFMA chain (0,4,1,5,2,6,3,7 inside groups of 8 channels), 2 per-offset chains then offset sum.
+    0 natural chain, 1 MFMA chain (0,4,1,5,2,6,3,7 inside groups of 8 channels), 2 per-offset chains then offset sum, 3 grouped.
     kind: 'k1' | 'k3' | 'k2s2' | 'k2s2T' | 'gen' | 'mlp'; n_out = output rows of the launch.  Tests hand this to the
     oracle to compare bit for bit."""
-    if kind == 'gen' and c2 == 0 and _packed_gen_ok(c1, c_out):
-        return 1
-    if kind == 'k3' and _split_k3_ok(c1, c2, c_out):
-        return 2
-    n_off = {'k3': 27, 'k2s2': 8}.get(kind, 1)
-    groups = 8 if kind in ('gen', 'k2s2T') else 1
-    if kind in ('k1', 'k3'):
-        plan = _pad_plan(c1, c2, c_out, n_out)
-        if plan is not None:
-            return ops.conv_order(plan[0], plan[1], plan[2], n_off, groups, n_out)
-    return ops.conv_order(c1, c2, c_out, n_off, groups, n_out)
+    form, shape = _layer_form(kind, c1, c2, c_out, n_out)
+    if form in ('gen', 'split'):
+        return 1 if form == 'gen' else 2
+    return ops.conv_order(*shape, {'k3': 27, 'k2s2': 8}.get(kind, 1), 8 if kind in ('gen', 'k2s2T') else 1)
 
 
 class _ConvBase(nn.Module):
@@ -819,33 +830,37 @@ class _ConvBase(nn.Module):
             return x
         return torch.nn.functional.pad(x, (0, width - x.shape[1]))
 
-    def _forward_autograd(self, x: SparseTensor, cm, src: _Map, coordinates, act: _Act, clip: float) -> SparseTensor:
-        """training path: the convolution as an autograd function (fastpcc_amd/autograd.py), epilogue as tensor ops"""
-        from .autograd import ConvSpec, sparse_conv
-        feats = x.F
+    def _resolve(self, cm, src: _Map, coordinates):
+        """-> (kind, dst map, child table): what the layer is on these maps -- 'gen' | 'k2s2T' | 'k1' | 'k3' | 'k2s2' -- its output map,
+        and for the two kinds that read one the [m][8] child_row table (the input map of 'k2s2T', the neighbour table of 'k2s2').
+        The tables of a 'k3' layer are not touched here: its evaluations differ in which of them they need built."""
         if self.GENERATIVE:
-            dst = cm._generated(src)
-            spec = ConvSpec('gen', src.n, dst.n)
-        elif self.TRANSPOSED:
+            return 'gen', cm._generated(src), None
+        if self.TRANSPOSED:
             if coordinates is None:
                 raise ValueError('a transposed convolution needs the target coordinate key')
             dst = cm._map(coordinates)
             if dst.parent is not src:
                 raise ValueError('target map is not a stride-2 child of the input map')
-            spec = ConvSpec('gen', src.n, dst.n) if dst.generated else ConvSpec('k2s2T', src.n, dst.n, dst.child_row)
-        elif self.ks == 1:
-            dst = src
-            spec = ConvSpec('k1', src.n, src.n)
-        elif self.ks == 3:
-            dst = src
+            return ('gen', dst, None) if dst.generated else ('k2s2T', dst, dst.child_row)
+        if self.ks == 1:
+            return 'k1', src, None
+        if self.ks == 3:
             if coordinates is not None and cm._map(coordinates) is not src:
                 raise NotImplementedError('stride-1 convolution onto a different coordinate map')
-            spec = ConvSpec('k3', src.n, src.n, cm._nbr27(src), cm._row_order(src, training=True))
-        else:
-            dst = cm._ensure_parent(src)
-            if src.generated:
-                raise NotImplementedError('stride-2 convolution of a generated set')
-            spec = ConvSpec('k2s2', src.n, dst.n, src.child_row)
+            return 'k3', src, None
+        dst = cm._ensure_parent(src)
+        if src.generated:
+            raise NotImplementedError('stride-2 convolution of a generated set')
+        return 'k2s2', dst, src.child_row
+
+    def _forward_autograd(self, x: SparseTensor, cm, src: _Map, coordinates, act: _Act, clip: float) -> SparseTensor:
+        """training path: the convolution as an autograd function (fastpcc_amd/autograd.py), epilogue as tensor ops"""
+        from .autograd import ConvSpec, sparse_conv
+        feats = x.F
+        kind, dst, table = self._resolve(cm, src, coordinates)
+        tables = (cm._nbr27(src), cm._row_order(src, training=True)) if kind == 'k3' else () if table is None else (table,)
+        spec = ConvSpec(kind, src.n, dst.n, *tables)
         if _fusable_in_training(act):
             from .autograd import sparse_conv_act
             out = sparse_conv_act(feats, self.kernel, self.bias, act.param if act.kind == ops.ACT_PRELU else None, spec, act.kind)
@@ -891,26 +906,34 @@ class _ConvBase(nn.Module):
             plan_rows = PAD_MIN_ROWS if any(padded) else 0
         return self._forward_fused(x, cm, src, coordinates, act, clip, plan_rows)
 
+    def _conv_padded(self, x1, x2, plan, n_out: int, act: _Act, clip: float, **table) -> torch.Tensor:
+        """the layer zero-padded to the MFMA shape `plan` (_pad_plan): padded inputs and weights in, the layer's own columns out"""
+        wp, bp = self._padded_weights(x1.shape[1], 0 if x2 is None else x2.shape[1], plan)
+        out = ops.conv_f32(self._pad_cols(x1, plan[0]), wp, plan[2], n_out, x2=self._pad_cols(x2, plan[1]), bias=bp, act=act.kind,
+                           slope=act.slope, clip=clip, pack=True, **table)[:, :self.out_channels]
+        # a narrow head (the 32 -> 1 classify layer of a two- or three-stage decoder on a map of PAD_MIN_ROWS rows or more) is read as a
+        # flat vector by the top-k pruning, which needs it contiguous
+        return out.contiguous() if self.out_channels < 8 else out
+
     def _forward_fused(self, x: SparseTensor, cm: CoordinateManager, src: _Map, coordinates: Optional[CoordinateMapKey], act: _Act,
                        clip: float, plan_rows: int) -> SparseTensor:
         """inference path: one fused launch.  plan_rows: the row count PAD_MIN_ROWS is compared with (the map's, or its clouds')"""
         parts = x.parts
         x1 = parts[0]
         x2 = parts[1] if len(parts) > 1 else None
-        derived = self._derived()
-        kw = dict(x2=x2, bias=derived['b'], act=act.kind, slope=act.slope, clip=clip, pack=True)
-        w = derived['w']
-        c_out = self.out_channels
-        if self.GENERATIVE:
-            dst = cm._generated(src)
-            d = self._derived()
-            if x2 is None and 'gen_w' in d:
+        c1, c2, c_out = x1.shape[1], (0 if x2 is None else x2.shape[1]), self.out_channels
+        d = self._derived()
+        w = d['w']
+        ep = dict(bias=d['b'], act=act.kind, slope=act.slope, clip=clip)          # the fused epilogue
+        kw = dict(x2=x2, pack=True, **ep)
+        kind, dst, table = self._resolve(cm, src, coordinates)
+        form, shape = _layer_form(kind, c1, c2, c_out, plan_rows)
+        if kind == 'gen':
+            if form == 'gen' and self.GENERATIVE:
                 # all 8 octant kernels side by side: one dense GEMM [n, C_in] @ [C_in, 8*C_out]; its row-major output IS
                 # the generated tensor [8n, C_out] (row 8*parent + octant)
-                halves = d['gen_w']
-                wide = 8 * c_out
-                out = torch.empty((src.n, wide), dtype=torch.float32, device=x1.device)
-                for h, wh in enumerate(halves):
+                out = torch.empty((src.n, 8 * c_out), dtype=torch.float32, device=x1.device)
+                for h, wh in enumerate(d['gen_w']):
                     cols = wh.shape[1]
                     bh = d['gen_b'][h] if d['gen_b'][0] is not None else None
                     ops.conv_f32(x1, wh, cols, src.n, bias=bh, act=act.kind, slope=act.slope, clip=clip,
@@ -918,86 +941,47 @@ class _ConvBase(nn.Module):
                 out = out.view(8 * src.n, c_out)
             else:
                 out = ops.conv_f32(x1, w, c_out, src.n, groups=8, **kw)
-        elif self.TRANSPOSED:
-            if coordinates is None:
-                raise ValueError('a transposed convolution needs the target coordinate key')
-            dst = cm._map(coordinates)
-            if dst.parent is not src:
-                raise ValueError('target map is not a stride-2 child of the input map')
-            if dst.generated:
-                out = ops.conv_f32(x1, w, c_out, src.n, groups=8, **kw)
+        elif kind == 'k2s2T':
+            order = None
+            if x2 is None and ops.conv_k2s2t_use_sparse(c1, c_out, dst.n):
+                order, sparse_table = cm._k2t_order(dst)       # over the children that exist: no octant is computed to be dropped
+            if order is not None:
+                out = ops.conv_k2s2t(x1, w, c_out, order, sparse_table, **ep)
             else:
-                order = table = None
-                if x2 is None and ops.conv_k2s2t_use_sparse(x1.shape[1], c_out, dst.n):
-                    order, table = cm._k2t_order(dst)      # over the children that exist: no octant is computed to be dropped
-                if order is not None:
-                    out = ops.conv_k2s2t(x1, w, c_out, order, table, bias=kw['bias'], act=act.kind, slope=act.slope, clip=clip)
-                else:
-                    out = ops.conv_f32(x1, w, c_out, src.n, groups=8, out_map=dst.child_row, om_os=8, om_gs=1,
-                                       out_rows=dst.n, **kw)
-        elif self.ks == 1:
-            dst = src
-            plan = _pad_plan(x1.shape[1], 0 if x2 is None else x2.shape[1], c_out, plan_rows)
-            if plan is not None:
-                wp, bp = self._padded_weights(x1.shape[1], 0 if x2 is None else x2.shape[1], plan)
-                out = ops.conv_f32(self._pad_cols(x1, plan[0]), wp, plan[2], src.n, x2=self._pad_cols(x2, plan[1]), bias=bp,
-                                   act=act.kind, slope=act.slope, clip=clip, pack=True)[:, :c_out]
-                if c_out < 8:
-                    # as in the 3x3x3 branch below: a narrow head (the 32 -> 1 classify layer of a two- or three-stage decoder on a
-                    # map of PAD_MIN_ROWS rows or more) is read as a flat vector by the top-k pruning, which needs it contiguous
-                    out = out.contiguous()
-            else:
-                out = ops.conv_f32(x1, w, c_out, src.n, **kw)
-        elif self.ks == 3:
-            dst = src
-            if coordinates is not None and cm._map(coordinates) is not src:
-                raise NotImplementedError('stride-1 convolution onto a different coordinate map')
-            d = self._derived()
-            plan = _pad_plan(x1.shape[1], 0 if x2 is None else x2.shape[1], c_out, plan_rows)
-            if x2 is None and 'k3_w' in d:
+                out = ops.conv_f32(x1, w, c_out, src.n, groups=8, out_map=table, om_os=8, om_gs=1, out_rows=dst.n, **kw)
+        elif kind == 'k1':
+            out = self._conv_padded(x1, x2, shape, src.n, act, clip) if form == 'pad' else ops.conv_f32(x1, w, c_out, src.n, **kw)
+        elif kind == 'k3':
+            if form == 'split':
                 y = ops.conv_f32(x1, d['k3_w'], 32, src.n, pack=True)       # per input row: its dot product with every offset's kernel
                 if src.generated and src.nbr27 is None and src.n == 8 * src.parent.n:
                     # a full generated set (the occupancy predictors' 8 candidates per voxel): the neighbour rows follow from the
                     # PARENT's table in registers -- the candidates' own table (108 bytes per row) is never written or read
-                    out = ops.gather_sum_generated(y, cm._nbr27(src.parent, True), bias=kw['bias'], act=act.kind, slope=act.slope, clip=clip)
+                    out = ops.gather_sum_generated(y, cm._nbr27(src.parent, True), **ep)
                 else:
-                    out = ops.gather_sum(y, cm._nbr27(src), 27, src.n, 1, src.n, bias=kw['bias'], act=act.kind,
-                                         slope=act.slope, clip=clip)
-            elif plan is not None:
-                wp, bp = self._padded_weights(x1.shape[1], 0 if x2 is None else x2.shape[1], plan)
-                ro = cm._row_order(src) if plan[0] + plan[1] > 16 else None
-                out = ops.conv_f32(self._pad_cols(x1, plan[0]), wp, plan[2], src.n, x2=self._pad_cols(x2, plan[1]), bias=bp,
-                                   act=act.kind, slope=act.slope, **cm._k3_table(src, True, ro),
-                                   clip=clip, row_order=ro, pack=True)[:, :c_out]
-                if c_out < 8:
-                    out = out.contiguous()
-            elif x2 is None and x1.shape[1] == 1 and getattr(x, '_fpcc_all_ones', False) and 4 <= c_out <= 32 and c_out % 4 == 0 \
+                    out = ops.gather_sum(y, cm._nbr27(src), 27, src.n, 1, src.n, **ep)
+            elif form == 'pad':
+                ro = cm._row_order(src) if shape[0] + shape[1] > 16 else None
+                out = self._conv_padded(x1, x2, shape, src.n, act, clip, **cm._k3_table(src, True, ro), row_order=ro)
+            elif x2 is None and c1 == 1 and getattr(x, '_fpcc_all_ones', False) and 4 <= c_out <= 32 and c_out % 4 == 0 \
                     and ops.conv_order(1, 0, c_out) == 0 and cm._mask27(src) is not None:
                 # the codec's first layer: every voxel carries the feature 1, so a row's sum only depends on WHICH neighbours
                 # exist -- evaluated from 27-bit masks (same FMA chain, same bits); the 108-byte-per-row neighbour table of the
                 # finest level is then never built
-                out = ops.conv_ones_k3(cm._mask27(src), w, c_out, bias=kw['bias'], act=act.kind, slope=act.slope, clip=clip)
+                out = ops.conv_ones_k3(cm._mask27(src), w, c_out, **ep)
             else:
                 # on the matrix pipe: an MFMA summation order, or order 0 on the natural-order matrix kernel (256-wide layers) -- either
                 # takes a row order and the row-major table in position order
-                c2 = 0 if x2 is None else x2.shape[1]
-                mfma = ops.conv_order(x1.shape[1], c2, c_out) != 0 or ops.conv_natural_matrix(x1.shape[1], c2, c_out, 27, 1)
+                mfma = bool(ops.conv_plan(c1, c2, c_out, 27, 1).matrix)
                 # 16 input channels: one 64-byte gather per neighbour -- Morton locality beats block skipping
-                ro = cm._row_order(src) if mfma and x1.shape[1] + (0 if x2 is None else x2.shape[1]) > 16 else None
-                out = ops.conv_f32(x1, w, c_out, src.n, **cm._k3_table(src, mfma and kw.get('pack', False) is True, ro), row_order=ro, **kw)
+                ro = cm._row_order(src) if mfma and c1 + c2 > 16 else None
+                out = ops.conv_f32(x1, w, c_out, src.n, **cm._k3_table(src, mfma, ro), row_order=ro, **kw)
         else:   # kernel 2, stride 2
-            dst = cm._ensure_parent(src)
-            if src.generated:
-                raise NotImplementedError('stride-2 convolution of a generated set')
-            c_in = x1.shape[1] + (0 if x2 is None else x2.shape[1])
             # (16 input channels: the one such layer -- 16 -> 64 onto the stride-2 map -- gains 0.19 ms per batch in pattern order and its
             # order costs more than that to build: measured, left in Morton order)
-            c2 = 0 if x2 is None else x2.shape[1]
-            if kw.get('pack', False) is True and c_in > 16 and (ops.conv_order(x1.shape[1], c2, c_out, 8, 1, dst.n) != 0 or
-                                                                  ops.conv_natural_matrix(x1.shape[1], c2, c_out, 8, 1)):
+            ro = None
+            if c1 + c2 > 16 and ops.conv_plan(c1, c2, c_out, 8, 1).matrix:
                 ro, table = cm._k2_order(src)              # shapes of the matrix pipe: parents in child-pattern order on large maps
-            else:
-                ro, table = None, src.child_row
             out = ops.conv_f32(x1, w, c_out, dst.n, nbr=table, n_offsets=8, nbr_ks=1, nbr_os=8, row_order=ro, **kw)
         return SparseTensor(out, coordinate_map_key=dst.key, coordinate_manager=cm)
 

@@ -88,6 +88,7 @@ _SIGS = {
     'fpcc_conv_f32_ws_bytes': (_i64, [_i32, _i32, _i32, _i32, _i32, _i64]),
     'fpcc_conv_f32_order': (_i32, [_i32, _i32, _i32]),
     'fpcc_conv_f32_order_ex': (_i32, [_i32, _i32, _i32, _i32, _i32, _i64]),
+    'fpcc_conv_f32_plan': (_i32, [_i32, _i32, _i32, _i32, _i32, _vp]),
     'fpcc_gather_sum_f32': (_i32, [_vp, _i32, _vp, _i32, _i64, _i64, _i64, _vp, _i32, _vp, _f32, _vp, _vp]),
     'fpcc_gather_sum_generated_f32': (_i32, [_vp, _i32, _vp, _i64, _vp, _i32, _vp, _f32, _vp, _vp]),
     'fpcc_logit_to_prob16': (_i32, [_vp, _i64, _vp, _vp]),
@@ -499,15 +500,13 @@ _PACKED_MAX = 1024
 
 def packed_weights(w: torch.Tensor, c1: int, c2: int, c_out: int, n_offsets: int, groups: int, fresh: bool = False) -> Optional[torch.Tensor]:
     """packed copy of w [groups, n_offsets, c1 + c2, c_out] for fpcc_conv_f32_pk, or None when the shape has no wave kernel: the
-    order-1 image (fpcc_conv_pack_weights_f32), or for the shapes of the natural-order matrix path (conv_natural_matrix) the
-    natural-order image (fpcc_conv_pack_weights_nat_f32) -- a shape has one or the other, never both.
+    order-1 image (fpcc_conv_pack_weights_f32), or for the shapes of the natural-order matrix path the natural-order image
+    (fpcc_conv_pack_weights_nat_f32): conv_plan(...).packed says which.
     fresh: pack now and do not cache (weights that change every step: training)"""
-    if lib().fpcc_conv_packed_floats(c1, c2, c_out, n_offsets, groups):
-        pack_fn = lib().fpcc_conv_pack_weights_f32
-    elif c_out == 256 and lib().fpcc_conv_packed_floats_nat(c1, c2, c_out, n_offsets, groups):
-        pack_fn = lib().fpcc_conv_pack_weights_nat_f32
-    else:
+    image = conv_plan(c1, c2, c_out, n_offsets, groups).packed
+    if not image:
         return None
+    pack_fn = lib().fpcc_conv_pack_weights_f32 if image == 1 else lib().fpcc_conv_pack_weights_nat_f32
     if fresh:
         out = torch.empty(w.numel(), dtype=torch.float32, device=w.device)
         _ok(pack_fn(w.data_ptr(), groups * n_offsets, c1 + c2, c_out, out.data_ptr(), _stream()))
@@ -587,7 +586,7 @@ def conv_set_tuning(which: int, value: int) -> int:
     (knob 7 apart, which needs FPCC_EXPERIMENT=1); a value a knob does not know -- knob 3 takes 0 and 16 only -- raises FpccError and
     leaves the knob as it was"""
     before = _ok(lib().fpcc_conv_set_tuning(int(which), int(value)))
-    conv_order.cache_clear()                    # knobs 4 / 7 (experiments only) move the summation-order thresholds
+    conv_plan.cache_clear()                     # knob 7 (experiments only) moves the summation order
     return before
 
 
@@ -695,9 +694,9 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
         om_os = groups
     ws, ws_bytes = None, 0
     wp = packed_weights(w, c1, c2, c_out, n_offsets, groups, fresh=(pack == 'fresh')) if pack else None
-    # a grouped (order 3) shape or one of the natural-order matrix path without a packed copy: room to pack into
-    if wp is None and ((nbr is not None and n_offsets >= 8) or c_out == 256):
-        ws_bytes = lib().fpcc_conv_f32_ws_bytes(c1, c2, c_out, n_offsets, groups, n_out)
+    if wp is None and n_out > 0:
+        # a grouped (order 3) shape or one of the natural-order matrix path without a packed copy: room to pack into
+        ws_bytes = conv_plan(c1, c2, c_out, n_offsets, groups).ws_bytes
         if ws_bytes:
             ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x1.device)
     # arguments first, start event last: on a host-paced stretch the GPU reaches the event before the host has launched the kernel,
@@ -715,8 +714,8 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
         _untraced_launch(fn, call)
         return out
     # 'mfma': whether the launch runs on the matrix pipe -- a summation order other than 0, or order 0 on the natural-order matrix kernel
-    on_matrix = bool(conv_order(c1, c2, c_out, n_offsets, groups, n_out)) or \
-        (conv_natural_matrix(c1, c2, c_out, n_offsets, groups) and conv_natural_uses_matrix(n_out * groups))
+    plan = conv_plan(c1, c2, c_out, n_offsets, groups)
+    on_matrix = plan.order != 0 or (plan.packed == 2 and conv_natural_uses_matrix(n_out * groups))
     _traced_launch(trace, fn, call, {'mfma': on_matrix, 'c_in': c1 + c2, 'c_out': c_out,
                                      'n_out': n_out, 'groups': groups, 'n_offsets': n_offsets, 'nbr': nbr,
                                      'nbr_ks': nbr_ks, 'nbr_os': nbr_os})
@@ -1228,16 +1227,32 @@ def table_conv_chunk(c_in: int, c_out: int, k: int) -> int:
     return k if k <= 27 else 16
 
 
+class ConvPlan(C.Structure):
+    """fpcc_conv_plan of include/fpcc_hip.h: order 0 | 1 | 3; matrix: a shape of the matrix pipe (takes a row order); packed: 0 no
+    packed weight image | 1 the order-1 image | 2 the natural-order image; ws_bytes: room a call without an image packs into"""
+    _fields_ = [('order', _i32), ('matrix', _i32), ('packed', _i32), ('chunk', _i32), ('packed_floats', _i64), ('ws_bytes', _i64)]
+
+
+ConvPlanValue = collections.namedtuple('ConvPlanValue', [f for f, _ in ConvPlan._fields_])      # what conv_plan hands out: immutable
+
+
 @functools.lru_cache(maxsize=8192)
+def conv_plan(c1: int, c2: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> ConvPlanValue:
+    """the library's one classification of a convolution shape (fpcc_conv_f32_plan): a function of the shape alone, never of a row
+    count -- cached per shape; conv_set_tuning clears the cache"""
+    plan = ConvPlan()
+    _ok(lib().fpcc_conv_f32_plan(c1, c2, c_out, n_offsets, groups, C.byref(plan)))
+    return ConvPlanValue(*(getattr(plan, f) for f in ConvPlanValue._fields))
+
+
 def conv_order(c1: int, c2: int, c_out: int, n_offsets: int = 1, groups: int = 1, n_out: int = 0) -> int:
-    return lib().fpcc_conv_f32_order_ex(c1, c2, c_out, n_offsets, groups, n_out)
+    return conv_plan(c1, c2, c_out, n_offsets, groups).order
 
 
-@functools.lru_cache(maxsize=8192)
 def conv_natural_matrix(c1: int, c2: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
-    """whether the shape belongs to the natural-order matrix path (fpcc_conv_f32_natural_matrix): summation order 0 -- conv_order()
-    stays 0 -- evaluated on MFMA; such a shape takes a row order and a packed (natural-order) weight image like the order-1 shapes"""
-    return bool(lib().fpcc_conv_f32_natural_matrix(c1, c2, c_out, n_offsets, groups))
+    """whether the shape belongs to the natural-order matrix path: summation order 0 -- conv_order() stays 0 -- evaluated on MFMA;
+    such a shape takes a row order and a packed (natural-order) weight image like the order-1 shapes"""
+    return conv_plan(c1, c2, c_out, n_offsets, groups).packed == 2
 
 
 def conv_natural_uses_matrix(rows: int) -> bool:

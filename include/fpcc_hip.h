@@ -191,11 +191,11 @@ int fpcc_numerics_version(void);
  * groups > 1 expresses a stride-2 transposed / generative convolution: group g = octant g of parent row o, with
  * out_map = child_row [m][8] ((om_os, om_gs) = (8, 1)) or NULL for the full generated set.
  *
- * Summation order (fixed, documented for bit-exact checking): see "Numerics version" above; fpcc_conv_f32_order_ex() reports
- * the order of a shape (0 natural chain, 1 MFMA chain, 3 grouped).  A grouped shape runs on the wave kernel and needs packed
- * weights: from the caller (fpcc_conv_f32_pk), or packed per call into a workspace of fpcc_conv_f32_ws_bytes() bytes; so does a
- * shape of the natural-order matrix path (below), with its own packed layout.
- * row_order (NULL: identity) is taken by every shape of the matrix pipe: fpcc_conv_f32_order() != 0 or fpcc_conv_f32_natural_matrix().
+ * Summation order (fixed, documented for bit-exact checking): see "Numerics version" above; fpcc_conv_f32_plan() reports the order
+ * of a shape (0 natural chain, 1 MFMA chain, 3 grouped) and everything else said here about shapes.  A grouped shape runs on the
+ * wave kernel and needs packed weights: from the caller (fpcc_conv_f32_pk), or packed per call into a workspace of plan.ws_bytes
+ * bytes; so does a shape of the natural-order matrix path (below), with its own packed layout.
+ * row_order (NULL: identity) is taken by every shape of the matrix pipe (plan.matrix).
  */
 int fpcc_conv_f32(const float *x1, int c1, int ld1, const float *x2, int c2, int ld2,
                   const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
@@ -211,6 +211,7 @@ int fpcc_conv_f32(const float *x1, int c1, int ld1, const float *x2, int c2, int
  * fpcc_conv_pack_weights_f32: w [n_mats][c_in][c_out] (n_mats = groups * n_offsets) ->
  *     w_packed[m][cc][g8][nb][h][i][j] = w[m][32 cc + 8 g8 + 4 h + j][32 nb + i]      (same number of floats);
  * the caller caches it next to the weights (fastpcc_amd/hipops.py keeps one per weight tensor). */
+/* see fpcc_conv_f32_plan, field packed_floats where packed == 1, else 0 */
 int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int groups);
 /* Natural-order matrix path: summation order 0 on v_mfma_f32_32x32x2_f32.  fpcc_conv_f32_natural_matrix() is 1 for the shapes it takes:
  *     C_out = 256;  c1, c2 multiples of 32 (c1 >= 32, c2 >= 0) with c1 + c2 <= 512;  1 <= n_offsets <= 27;  groups 1 or 8
@@ -228,6 +229,7 @@ int64_t fpcc_conv_packed_floats(int c1, int c2, int c_out, int n_offsets, int gr
  * a workspace of fpcc_conv_f32_ws_bytes() bytes, or whose rows are not 16-byte aligned (ld % 4), runs on the VALU kernel as before.
  * fpcc_conv_natural_use_matrix: 1 when knob 15 sends such a shape with `rows` output rows x groups to the matrix kernel, else 0.
  * fpcc_conv_natural_launches: diagnostics, launches of the natural-order matrix kernel by this process so far (tests). */
+/* see fpcc_conv_f32_plan: packed == 2, and field packed_floats where packed == 2, else 0 */
 int fpcc_conv_f32_natural_matrix(int c1, int c2, int c_out, int n_offsets, int groups);
 int64_t fpcc_conv_packed_floats_nat(int c1, int c2, int c_out, int n_offsets, int groups);
 int fpcc_conv_pack_weights_nat_f32(const float *w, int64_t n_mats, int c_in, int c_out, float *w_packed, void *stream);
@@ -394,19 +396,30 @@ int fpcc_conv_tile_keys(const uint32_t *row_masks, int n_offsets, const int32_t 
 int fpcc_conv_group_order(const int64_t *group_keys, int64_t n_groups, int32_t *perm_out, void *stream);
 int fpcc_conv_regroup_rows(const int32_t *row_order, const int32_t *group_perm, int64_t n, int group, int32_t *row_order_out,
                            void *stream);
-/* Workspace the shape needs (0 for most).  Multi-offset convolutions (8 <= n_offsets <= 27, groups == 1, C_out in
- * {32, 64, 128}) on maps of at most 8192 rows are evaluated offset-split: one workgroup per (row tile, kernel offset)
- * writes raw partial sums to ws[n_offsets][n_out][c_out], a second kernel reduces them (order 2 below).  Small pyramid
- * levels otherwise run as a few workgroups walking a long serial chain of stages.  The caller owns ws (16-byte aligned). */
-int64_t fpcc_conv_f32_ws_bytes(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out);
-int fpcc_conv_f32_order(int c1, int c2, int c_out);
-/* Same, including the launch-dependent choice: the offset-split shapes of fpcc_conv_f32_ws_bytes have order 2
- * (per-offset FMA chains from zero in the MFMA channel order, partial sums added in ascending offset order, then the
- * bias).
+/* THE classification of a convolution shape (numerics version 3): where fpcc_conv_f32 / fpcc_conv_f32_pk evaluate it, in which
+ * summation order, which packed weight image it reads.  A function of (c1, c2, c_out, n_offsets, groups) and of knob 7 (experiments
+ * only) -- never of a row count, of the caller's operands or of another knob -- so a caller may cache it per shape.  The one question
+ * that does depend on rows is fpcc_conv_natural_use_matrix(rows).  Every other shape query of this header reads one field of it.
+ * fpcc_conv_f32_plan fills *plan and returns FPCC_OK (FPCC_E_ARG for a NULL plan).
  * INVARIANT for callers that batch independent clouds in one launch: since numerics version 2 the order is a function of the
- * layer's SHAPE alone (n_out is accepted and ignored); the one rule above this interface that does look at a row count
- * (FPCC_PAD_MIN_ROWS, zero-padding of narrow shapes) must be applied to the rows of the cloud a row belongs to, not of the launch:
- * an encoder and a decoder may batch different sets of clouds together and must still agree bit for bit. */
+ * layer's SHAPE alone; the one rule above this interface that does look at a row count (FPCC_PAD_MIN_ROWS, zero-padding of narrow
+ * shapes) must be applied to the rows of the cloud a row belongs to, not of the launch: an encoder and a decoder may batch different
+ * sets of clouds together and must still agree bit for bit. */
+typedef struct fpcc_conv_plan {
+    int32_t order;          /* summation order: 0 natural chain | 1 MFMA chain | 3 grouped ("Numerics version" above) */
+    int32_t matrix;         /* 1: a shape of the matrix pipe -- order != 0, or order 0 on the natural-order matrix kernel; takes a row_order */
+    int32_t packed;         /* packed weight image fpcc_conv_f32_pk reads: 0 none | 1 fpcc_conv_pack_weights_f32 | 2 fpcc_conv_pack_weights_nat_f32 */
+    int32_t chunk;          /* input channels per MFMA stage of an order 1 / 3 shape: 16 | 32, else 0 */
+    int64_t packed_floats;  /* floats of that image (those of the weights); 0 when packed == 0 */
+    int64_t ws_bytes;       /* workspace (16-byte aligned, the caller's) a call WITHOUT an image packs into: order 3 shapes (required) and
+                             * natural-order matrix shapes (else they run on the VALU kernel); 0: the shape runs without an image */
+} fpcc_conv_plan;
+int fpcc_conv_f32_plan(int c1, int c2, int c_out, int n_offsets, int groups, fpcc_conv_plan *plan);
+/* see fpcc_conv_f32_plan, field ws_bytes (0 for n_out <= 0) */
+int64_t fpcc_conv_f32_ws_bytes(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out);
+/* see fpcc_conv_f32_plan, field order, of the shape with one offset and one group */
+int fpcc_conv_f32_order(int c1, int c2, int c_out);
+/* see fpcc_conv_f32_plan, field order (n_out is accepted and ignored) */
 int fpcc_conv_f32_order_ex(int c1, int c2, int c_out, int n_offsets, int groups, int64_t n_out);
 
 /* Weight gradient of the same operator (training; MinkowskiEngine's autograd backward, reached from

@@ -67,7 +67,7 @@ def test_struct_layouts_match_the_header(tmp_path):
     fpcc_conv_i8_also): sizes and field offsets as a C compiler lays out include/fpcc_hip.h"""
     import subprocess
     mirrors = {'fpcc_i8_layer': hipops.I8Layer, 'fpcc_i8_requant': hipops.I8Requant, 'fpcc_int_onescale': hipops.IntOneScale,
-               'fpcc_requant8': hipops._Requant8}
+               'fpcc_requant8': hipops._Requant8, 'fpcc_conv_plan': hipops.ConvPlan}
     lines = []
     for c_name, cls in mirrors.items():
         lines.append(f'printf("{c_name} size %zu\\n", sizeof({c_name}));')

@@ -46,7 +46,7 @@ def main():
         x2 = kw.get('x2')
         c2 = 0 if x2 is None else x2.shape[1]
         k, g = kw.get('n_offsets', 1), kw.get('groups', 1)
-        if n_out > 0 and ops.conv_natural_matrix(c1, c2, c_out, k, g):
+        if n_out > 0 and ops.conv_plan(c1, c2, c_out, k, g).packed == 2:
             kind = 'k3' if k == 27 else 'k2s2' if k == 8 else ('k2s2T' if kw.get('out_map') is not None else 'gen') if g == 8 else 'k1'
             key = (kind, c1, c2, n_out, kw.get('row_order') is not None)
             if key not in seen:
