@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""DDP training throughput of lossy_coord_v2 (baseline_r1 by default; --model baseline_r3 | baseline_r5) on synthetic ShapeNet-like batches (BASELINE.json configs[4]).
+"""DDP training throughput of lossy_coord_v2 (baseline_r1 by default; --model baseline_r3 | baseline_r5 | expanded_r3 | expanded_r5) on synthetic ShapeNet-like batches (BASELINE.json configs[4]).
 
     python bench_train.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
@@ -22,7 +22,7 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--resolution', type=int, default=128)
-    ap.add_argument('--model', choices=('baseline_r1', 'baseline_r3', 'baseline_r5'), default='baseline_r1')
+    ap.add_argument('--model', choices=('baseline_r1', 'baseline_r3', 'baseline_r5', 'expanded_r3', 'expanded_r5'), default='baseline_r1')
     ap.add_argument('--amp-dtype', choices=('', 'bfloat16'), default='',
                     help="operand dtype of the training convolutions (train.amp_dtype): '' = fp32, bfloat16 = bf16 MFMA, fp32 accumulation")
     args = ap.parse_args()

@@ -170,7 +170,9 @@ def _strided_rows(t: torch.Tensor) -> bool:
 
 
 def _mfma(c_in: int, c_out: int) -> bool:
-    return ops.conv_order(c_in, 0, c_out) != 0
+    """the 3x3x3 convolution of this shape runs on the matrix pipe and takes a row order: the order-1 / order-3 shapes and the
+    natural-order matrix shapes (256 columns; order 0 is a sum per row, so its bits do not depend on the row order)"""
+    return bool(ops.conv_plan(c_in, 0, c_out, 27, 1).matrix)
 
 
 def _k3_one_channel(x: torch.Tensor, w: torch.Tensor, s: ConvSpec, **epilogue) -> torch.Tensor:
@@ -442,7 +444,7 @@ class LinearActFn(torch.autograd.Function):
         if ctx.needs_input_grad[1] and x.dtype is not torch.bfloat16:
             if c_in in (32, 64, 128) and c_out % 64 == 0:        # shapes the matrix-core gradient kernel takes with the operands swapped
                 dw = ops.conv_wgrad(g, x, n).view(c_out, c_in)
-            else:                                                # (a 256-wide input: its own orientation, transposed as a view)
+            else:       # (a 256- or 512-wide input: its own orientation, a matrix launch too for 256 outputs, transposed as a view)
                 dw = ops.conv_wgrad(x, g, n).view(c_in, c_out).t()
         if dbias is not None:
             dbias = dbias.view(ctx.bias_shape)

@@ -6,7 +6,8 @@ method names and the frame layout of `PCC` in /root/reference/models/convolution
     test_forward(PCData)      -> dict with the reconstructed cloud, the bytes and the two wall-clock times, timed the
                                  way the reference's Timer blocks are (device synchronised at both ends).
 
-Training (`train_forward`) is not part of this inference build.
+Training: `forward` in train mode is the reference's `train_forward` (noisy bottleneck, the decoder's stages on the kept candidates, the
+loss terms); fastpcc_amd/train.py drives it for every name of `train.V2_MODELS`.
 """
 import io
 import time

@@ -13,6 +13,8 @@
 // columns, one wave per 32-column block; the reduction dimension of this GEMM is the ROW index, so both operands are
 // read straight from global memory as 128-byte row segments (lane = channel / column), two rows per MFMA k-step.
 // Row splits write partial sums; k_wgrad_reduce adds them in ascending split order (fixed association, reproducible).
+// C_out = 256 (the expanded rate points): the same row walk and the same row splits with two column blocks per wave, so the column
+// halves of dW are bit for bit the 128-column launches on the halves of dY; fpcc_conv_wgrad_matrix says which shapes run here.
 #include "common.h"
 
 #include <algorithm>
@@ -35,6 +37,12 @@ struct WgradArgs {
 
 __device__ float g_wgrad_zero[128];
 
+// B operand of a wave that owns NP column blocks: NP adjacent columns in one load
+template <int NP> struct BCols { typedef float type __attribute__((ext_vector_type(NP))); };
+template <> struct BCols<1> { typedef float type; };
+__device__ __forceinline__ float b_col(float v, int) { return v; }
+template <class V> __device__ __forceinline__ float b_col(const V &v, int p) { return v[p]; }
+
 __device__ __forceinline__ void row_pair(const WgradArgs &a, int k, int g, int64_t r, int64_t end, int64_t &in_row,
                                          int64_t &out_row) {
     in_row = out_row = -1;
@@ -45,11 +53,13 @@ __device__ __forceinline__ void row_pair(const WgradArgs &a, int k, int g, int64
     }
 }
 
-template <int NBT>
+// NH = 2 (256 output columns): blockIdx.z also carries a column-half index, the workgroup's waves own columns 128 half + 32 wave ...
+template <int NBT, int NH = 1>
 __global__ __launch_bounds__(64 * NBT) void k_wgrad_mfma(WgradArgs a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    const int s = blockIdx.x, kg = blockIdx.y, cb = blockIdx.z;
+    const int s = blockIdx.x, kg = blockIdx.y, cb = NH == 1 ? blockIdx.z : blockIdx.z / NH;
+    const int half0 = NH == 1 ? 0 : 32 * NBT * (int)(blockIdx.z % NH);      // first column of this workgroup's half
     const int g = kg / a.n_off, k = kg % a.n_off;
     const int64_t begin = (int64_t)s * a.rows_per_split;
     const int64_t end = min(begin + a.rows_per_split, a.n);
@@ -64,14 +74,14 @@ __global__ __launch_bounds__(64 * NBT) void k_wgrad_mfma(WgradArgs a) {
             int64_t in_row, out_row;
             row_pair(a, k, g, base + 2 * j + lh, end, in_row, out_row);
             const float *px = in_row >= 0 ? a.x + in_row * a.ldx + 32 * cb + li : g_wgrad_zero + li;
-            const float *pd = out_row >= 0 ? a.dy + out_row * a.ldy + 32 * wave + li : g_wgrad_zero + li;
+            const float *pd = out_row >= 0 ? a.dy + out_row * a.ldy + 32 * wave + li + half0 : g_wgrad_zero + li;
             av[j] = *px;
             bv[j] = *pd;
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
     }
-    float *dst = a.partial + (((int64_t)s * a.groups * a.n_off + kg) * a.c_in + 32 * cb) * a.c_out + 32 * wave + li;
+    float *dst = a.partial + (((int64_t)s * a.groups * a.n_off + kg) * a.c_in + 32 * cb) * a.c_out + 32 * wave + li + half0;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
         const int ci = (reg & 3) + 8 * (reg >> 2) + 4 * lh;
@@ -84,46 +94,57 @@ __global__ __launch_bounds__(64 * NBT) void k_wgrad_mfma(WgradArgs a) {
 // load per row), block q holding channel CB*i + q -- a permutation of the channel <-> M-index assignment that costs
 // nothing at the store.  Every X row is read once per wave (L1-shared by the workgroup's waves) and every dY row once per
 // workgroup: 1/(2*CB) of the L2 traffic of the per-block kernel above.
-template <int NBT, int CB>
+// NP = 2 (256 output columns): wave w owns the two column blocks 64 w .. 64 w + 63; lane i of the B operand carries columns 2 i and
+// 2 i + 1 (one 8-byte load per row), block p holding column 2 i + p, so every X load feeds 2 CB MFMAs.  Per element of dW the MFMA
+// chain over the rows is the one of the 128-column launch on that half of dY -- same bits.
+template <int NBT, int CB, int NP = 1>
 __global__ __launch_bounds__(64 * NBT) void k_wgrad_mfma_wide(WgradArgs a) {
     typedef float fvec __attribute__((ext_vector_type(CB)));
+    typedef typename BCols<NP>::type dvec;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const int s = blockIdx.x, kg = blockIdx.y, cg = blockIdx.z;
     const int g = kg / a.n_off, k = kg % a.n_off;
     const int64_t begin = (int64_t)s * a.rows_per_split;
     const int64_t end = min(begin + a.rows_per_split, a.n);
-    f32x16 acc[CB];
+    f32x16 acc[NP][CB];
 #pragma unroll
-    for (int q = 0; q < CB; ++q)
+    for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
+        for (int q = 0; q < CB; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.0f;
 
     for (int64_t base = begin; base < end; base += 32) {
         fvec av[16];
-        float bv[16];
+        dvec bv[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             int64_t in_row, out_row;
             row_pair(a, k, g, base + 2 * j + lh, end, in_row, out_row);
             const float *px = in_row >= 0 ? a.x + in_row * a.ldx + 32 * CB * cg + CB * li : g_wgrad_zero + CB * li;
-            const float *pd = out_row >= 0 ? a.dy + out_row * a.ldy + 32 * wave + li : g_wgrad_zero + li;
+            const float *pd = out_row >= 0 ? a.dy + out_row * a.ldy + 32 * NP * wave + NP * li : g_wgrad_zero + NP * li;
             av[j] = *reinterpret_cast<const fvec *>(px);
-            bv[j] = *pd;
+            bv[j] = *reinterpret_cast<const dvec *>(pd);
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j)
 #pragma unroll
-            for (int q = 0; q < CB; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][q], bv[j], acc[q], 0, 0, 0);
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int q = 0; q < CB; ++q)
+                    acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][q], b_col(bv[j], p), acc[p][q], 0, 0, 0);
     }
-    float *dst = a.partial + (((int64_t)s * a.groups * a.n_off + kg) * a.c_in + 32 * CB * cg) * a.c_out + 32 * wave + li;
+    float *dst = a.partial + (((int64_t)s * a.groups * a.n_off + kg) * a.c_in + 32 * CB * cg) * a.c_out + 32 * NP * wave + NP * li;
 #pragma unroll
-    for (int q = 0; q < CB; ++q)
+    for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * lh;            // M index of the accumulator row
-            dst[(int64_t)(CB * m + q) * a.c_out] = acc[q][reg];
-        }
+        for (int q = 0; q < CB; ++q)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int m = (reg & 3) + 8 * (reg >> 2) + 4 * lh;            // M index of the accumulator row
+                dst[(int64_t)(CB * m + q) * a.c_out + p] = acc[p][q][reg];
+            }
 }
 
 // 3x3x3-style maps given in neighbour-pattern row order (fpcc_conv_row_keys): the rows that have kernel offset k are
@@ -149,21 +170,30 @@ __global__ __launch_bounds__(256) void k_wgrad_blockmask(const int32_t *__restri
     if (lane == 0) masks[b] = m;
 }
 
-template <int NBT, int CB>
-__global__ __launch_bounds__(64 * NBT, 2) void k_wgrad_rows(WgradArgs a, const uint32_t *__restrict__ masks,
+// 256 output columns: NP = 2 as k_wgrad_mfma_wide; where dY's rows are not 8-byte aligned, NH = 2 as k_wgrad_mfma (blockIdx.z also
+// carries a column-half index) -- the row walk, hence the bits, must not depend on the operands' alignment.
+// Two workgroups per CU as in the 128-column form, except NP = 2 with CB = 4: its 8 x 16 accumulator registers plus two half blocks of
+// operands in flight (96 registers) do not fit 256 registers a wave and spilled 16 bytes per lane under (256, 2); built for one
+// workgroup per CU it takes 134 + 128 registers and no scratch.
+template <int NBT, int CB, int NP = 1, int NH = 1>
+__global__ __launch_bounds__(64 * NBT, NP * CB == 8 ? 1 : 2) void k_wgrad_rows(WgradArgs a, const uint32_t *__restrict__ masks,
                                                             const int32_t *__restrict__ row_order) {
     typedef float fvec __attribute__((ext_vector_type(CB)));
+    typedef typename BCols<NP>::type dvec;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int li = lane & 31, lh = lane >> 5;
-    const int s = blockIdx.x, k = blockIdx.y, cg = blockIdx.z;
+    const int s = blockIdx.x, k = blockIdx.y, cg = NH == 1 ? blockIdx.z : blockIdx.z / NH;
+    const int half0 = NH == 1 ? 0 : 32 * NBT * (int)(blockIdx.z % NH);
     // row split s takes blocks s, s + splits, ...: in pattern order the rows that have an offset are clustered, a
     // contiguous range per split would give some workgroups all of an offset's blocks and others none
     const int64_t b_begin = s, b_end = (a.n + 31) / 32, b_step = a.splits;
-    f32x16 acc[CB];
+    f32x16 acc[NP][CB];
 #pragma unroll
-    for (int q = 0; q < CB; ++q)
+    for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[q][r] = 0.0f;
+        for (int q = 0; q < CB; ++q)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.0f;
 
     auto next_active = [&](int64_t b) {
         while (b < b_end && !((masks[b] >> k) & 1u)) b += b_step;
@@ -176,29 +206,32 @@ __global__ __launch_bounds__(64 * NBT, 2) void k_wgrad_rows(WgradArgs a, const u
         in_row = out_row >= 0 ? a.nbr[(int64_t)k * a.nbr_ks + (int64_t)out_row * a.nbr_os] : -1;
         if (in_row < 0) out_row = -1;
     };
-    auto load_half = [&](int half, int32_t in_row, int32_t out_row, fvec (&av)[8], float (&bv)[8]) {
+    auto load_half = [&](int half, int32_t in_row, int32_t out_row, fvec (&av)[8], dvec (&bv)[8]) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int src = 16 * half + 2 * j + lh;
             const int32_t ir = __shfl(in_row, src), orow = __shfl(out_row, src);
             const float *px = ir >= 0 ? a.x + (int64_t)ir * a.ldx + 32 * CB * cg + CB * li : g_wgrad_zero + CB * li;
-            const float *pd = orow >= 0 ? a.dy + (int64_t)orow * a.ldy + 32 * wave + li : g_wgrad_zero + li;
+            const float *pd = orow >= 0 ? a.dy + (int64_t)orow * a.ldy + 32 * NP * wave + NP * li + half0 : g_wgrad_zero + NP * li;
             av[j] = *reinterpret_cast<const fvec *>(px);
-            bv[j] = *pd;
+            bv[j] = *reinterpret_cast<const dvec *>(pd);
         }
     };
-    auto mma_half = [&](const fvec (&av)[8], const float (&bv)[8]) {
+    auto mma_half = [&](const fvec (&av)[8], const dvec (&bv)[8]) {
 #pragma unroll
         for (int j = 0; j < 8; ++j)
 #pragma unroll
-            for (int q = 0; q < CB; ++q) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][q], bv[j], acc[q], 0, 0, 0);
+            for (int p = 0; p < NP; ++p)
+#pragma unroll
+                for (int q = 0; q < CB; ++q)
+                    acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j][q], b_col(bv[j], p), acc[p][q], 0, 0, 0);
     };
 
     int64_t b = next_active(b_begin);
     if (b < b_end) {
         int32_t in_row, out_row, in_next, out_next;
         fvec av0[8], av1[8];
-        float bv0[8], bv1[8];
+        dvec bv0[8], bv1[8];
         load_rows(b, in_row, out_row);
         load_half(0, in_row, out_row, av0, bv0);
         for (;;) {
@@ -215,14 +248,16 @@ __global__ __launch_bounds__(64 * NBT, 2) void k_wgrad_rows(WgradArgs a, const u
             out_row = out_next;
         }
     }
-    float *dst = a.partial + (((int64_t)s * a.n_off + k) * a.c_in + 32 * CB * cg) * a.c_out + 32 * wave + li;
+    float *dst = a.partial + (((int64_t)s * a.n_off + k) * a.c_in + 32 * CB * cg) * a.c_out + 32 * NP * wave + NP * li + half0;
 #pragma unroll
-    for (int q = 0; q < CB; ++q)
+    for (int p = 0; p < NP; ++p)
 #pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int m = (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-            dst[(int64_t)(CB * m + q) * a.c_out] = acc[q][reg];
-        }
+        for (int q = 0; q < CB; ++q)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int m = (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+                dst[(int64_t)(CB * m + q) * a.c_out + p] = acc[p][q][reg];
+            }
 }
 
 // any channel counts: thread = a few (ci, co) pairs, rows walked serially (row maps are wave-uniform scalar loads)
@@ -335,18 +370,40 @@ int pick_splits(int c_in, int c_out, int kg, int64_t n, bool mfma) {
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
-bool wgrad_mfma_ok(int c_in, int c_out) { return c_in % 32 == 0 && (c_out == 32 || c_out == 64 || c_out == 128); }
+// k_wgrad_rows<waves, CB[, 2]> for c_out = 64 | 128 | 256 (with 32 columns a workgroup would be one wave: those shapes stay on
+// k_wgrad_mfma_wide) and k_wgrad_mfma_wide<waves, CB[, 2]> for c_out = 32 | 64 | 128 | 256, on `cgs` input-channel groups
+template <int CB>
+void launch_rows(const WgradArgs &a, int kg, int cgs, const uint32_t *masks, const int32_t *row_order, hipStream_t s) {
+    const dim3 grid(a.splits, kg, cgs);
+    if (a.c_out == 256) hipLaunchKernelGGL((k_wgrad_rows<4, CB, 2>), grid, dim3(256), 0, s, a, masks, row_order);
+    else if (a.c_out == 128) hipLaunchKernelGGL((k_wgrad_rows<4, CB>), grid, dim3(256), 0, s, a, masks, row_order);
+    else hipLaunchKernelGGL((k_wgrad_rows<2, CB>), grid, dim3(128), 0, s, a, masks, row_order);
+}
+
+template <int CB>
+void launch_wide(const WgradArgs &a, int kg, int cgs, hipStream_t s) {
+    const dim3 grid(a.splits, kg, cgs);
+    if (a.c_out == 256) hipLaunchKernelGGL((k_wgrad_mfma_wide<4, CB, 2>), grid, dim3(256), 0, s, a);
+    else if (a.c_out == 128) hipLaunchKernelGGL((k_wgrad_mfma_wide<4, CB>), grid, dim3(256), 0, s, a);
+    else if (a.c_out == 64) hipLaunchKernelGGL((k_wgrad_mfma_wide<2, CB>), grid, dim3(128), 0, s, a);
+    else hipLaunchKernelGGL((k_wgrad_mfma_wide<1, CB>), grid, dim3(64), 0, s, a);
+}
 
 }  // namespace
 }  // namespace fpcc
 
 using namespace fpcc;
 
+extern "C" int fpcc_conv_wgrad_matrix(int c_in, int c_out) {
+    return c_in >= 32 && c_in % 32 == 0 && (c_out == 32 || c_out == 64 || c_out == 128 || c_out == 256);
+}
+
 extern "C" int64_t fpcc_conv_wgrad_ws_bytes(int c_in, int c_out, int n_offsets, int groups, int64_t n) {
     if (c_in < 1 || c_out < 1 || n_offsets < 1 || groups < 1 || n < 0) return FPCC_E_ARG;
     const int kg = n_offsets * groups;
-    const int splits = pick_splits(c_in, c_out, kg, n, wgrad_mfma_ok(c_in, c_out));
+    const int splits = pick_splits(c_in, c_out, kg, n, fpcc_conv_wgrad_matrix(c_in, c_out) != 0);
     return (int64_t)splits * kg * c_in * c_out * 4 + ((n + 31) / 32 + 4) * 4;      // partial sums + one mask per 32 rows
 }
 
@@ -367,7 +424,7 @@ extern "C" int fpcc_conv_wgrad_f32(const float *x, int c_in, int ldx, const floa
         return FPCC_OK;
     }
     if (!x || !dy) return fail_arg("conv_wgrad: null pointer");
-    const bool mfma = wgrad_mfma_ok(c_in, c_out);
+    const bool mfma = fpcc_conv_wgrad_matrix(c_in, c_out) != 0;
     const int splits = pick_splits(c_in, c_out, kg, n, mfma);
     const int64_t need = (int64_t)splits * count * 4 + ((n + 31) / 32 + 4) * 4;
     if (!ws || ws_bytes < need) return fail_arg("conv_wgrad: workspace of fpcc_conv_wgrad_ws_bytes() bytes required");
@@ -375,35 +432,31 @@ extern "C" int fpcc_conv_wgrad_f32(const float *x, int c_in, int ldx, const floa
     WgradArgs a{x, c_in, ldx, dy, c_out, ldy, nbr, n_offsets, nbr_ks, nbr_os, out_map, om_os, om_gs, groups, n,
                 rows_per_split, splits, static_cast<float *>(ws)};
     static const int skip_rows = [] { const char *e = getenv("FPCC_WGRAD_ROWS"); return e ? atoi(e) : 1; }();
-    if (skip_rows && mfma && row_order && nbr && !out_map && groups == 1 && n_offsets <= 32 && c_in % 64 == 0 && aligned16(x) &&
-        ldx % 4 == 0 && (c_out == 128 || c_out == 64)) {
+    const bool x16 = aligned16(x) && ldx % 4 == 0;                              // the 16- and 8-byte X loads
+    const bool pair = c_out == 256 && aligned8(dy) && ldy % 2 == 0;            // the 8-byte dY loads of the two-block waves
+    if (skip_rows && mfma && row_order && nbr && !out_map && groups == 1 && n_offsets <= 32 && c_in % 64 == 0 && x16 &&
+        (c_out == 64 || c_out == 128 || c_out == 256)) {
         uint32_t *masks = reinterpret_cast<uint32_t *>(static_cast<float *>(ws) + (int64_t)splits * count);
         const int64_t n_blocks = (n + 31) / 32;
         hipLaunchKernelGGL(k_wgrad_blockmask, dim3(blocks_for(n_blocks, 4)), dim3(256), 0, s, nbr, n_offsets, nbr_ks, nbr_os,
                            row_order, n, n_blocks, masks);
         if (int rc = check_hip(hipGetLastError(), "k_wgrad_blockmask")) return rc;
-        if (c_in % 128 == 0) {
-            const dim3 grid(splits, kg, c_in / 128);
-            if (c_out == 128) hipLaunchKernelGGL((k_wgrad_rows<4, 4>), grid, dim3(256), 0, s, a, masks, row_order);
-            else hipLaunchKernelGGL((k_wgrad_rows<2, 4>), grid, dim3(128), 0, s, a, masks, row_order);
+        if (c_out == 256 && !pair) {
+            if (c_in % 128 == 0) hipLaunchKernelGGL((k_wgrad_rows<4, 4, 1, 2>), dim3(splits, kg, 2 * (c_in / 128)), dim3(256), 0, s, a, masks, row_order);
+            else hipLaunchKernelGGL((k_wgrad_rows<4, 2, 1, 2>), dim3(splits, kg, 2 * (c_in / 64)), dim3(256), 0, s, a, masks, row_order);
+        } else if (c_in % 128 == 0) {
+            launch_rows<4>(a, kg, c_in / 128, masks, row_order, s);
         } else {
-            const dim3 grid(splits, kg, c_in / 64);
-            if (c_out == 128) hipLaunchKernelGGL((k_wgrad_rows<4, 2>), grid, dim3(256), 0, s, a, masks, row_order);
-            else hipLaunchKernelGGL((k_wgrad_rows<2, 2>), grid, dim3(128), 0, s, a, masks, row_order);
+            launch_rows<2>(a, kg, c_in / 64, masks, row_order, s);
         }
-    } else if (mfma && c_in % 128 == 0 && aligned16(x) && ldx % 4 == 0) {
-        const dim3 grid(splits, kg, c_in / 128);
-        if (c_out == 128) hipLaunchKernelGGL((k_wgrad_mfma_wide<4, 4>), grid, dim3(256), 0, s, a);
-        else if (c_out == 64) hipLaunchKernelGGL((k_wgrad_mfma_wide<2, 4>), grid, dim3(128), 0, s, a);
-        else hipLaunchKernelGGL((k_wgrad_mfma_wide<1, 4>), grid, dim3(64), 0, s, a);
-    } else if (mfma && c_in % 64 == 0 && aligned16(x) && ldx % 4 == 0) {
-        const dim3 grid(splits, kg, c_in / 64);
-        if (c_out == 128) hipLaunchKernelGGL((k_wgrad_mfma_wide<4, 2>), grid, dim3(256), 0, s, a);
-        else if (c_out == 64) hipLaunchKernelGGL((k_wgrad_mfma_wide<2, 2>), grid, dim3(128), 0, s, a);
-        else hipLaunchKernelGGL((k_wgrad_mfma_wide<1, 2>), grid, dim3(64), 0, s, a);
+    } else if (mfma && c_in % 128 == 0 && x16 && (c_out < 256 || pair)) {
+        launch_wide<4>(a, kg, c_in / 128, s);
+    } else if (mfma && c_in % 64 == 0 && x16 && (c_out < 256 || pair)) {
+        launch_wide<2>(a, kg, c_in / 64, s);
     } else if (mfma) {
         const dim3 grid(splits, kg, c_in / 32);
-        if (c_out == 128) hipLaunchKernelGGL((k_wgrad_mfma<4>), grid, dim3(256), 0, s, a);
+        if (c_out == 256) hipLaunchKernelGGL((k_wgrad_mfma<4, 2>), dim3(splits, kg, 2 * (c_in / 32)), dim3(256), 0, s, a);
+        else if (c_out == 128) hipLaunchKernelGGL((k_wgrad_mfma<4>), grid, dim3(256), 0, s, a);
         else if (c_out == 64) hipLaunchKernelGGL((k_wgrad_mfma<2>), grid, dim3(128), 0, s, a);
         else hipLaunchKernelGGL((k_wgrad_mfma<1>), grid, dim3(64), 0, s, a);
     } else if (!launch_small(a, splits, kg, s)) {

@@ -75,6 +75,7 @@ _SIGS = {
     'fpcc_conv_wgrad_ws_bytes': (_i64, [_i32, _i32, _i32, _i32, _i64]),
     'fpcc_conv_wgrad_f32': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp,
                                    _i32, _vp, _i64, _vp]),
+    'fpcc_conv_wgrad_matrix': (_i32, [_i32, _i32]),
     'fpcc_epilogue_bwd_ws_bytes': (_i64, [_i64, _i32]),
     'fpcc_epilogue_bwd_f32': (_i32, [_vp, _i32, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_noisy_normal_ws_bytes': (_i64, [_i64]),
@@ -1020,6 +1021,13 @@ def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch
                               _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
                               _stream()))
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def conv_wgrad_matrix(c_in: int, c_out: int) -> bool:
+    """whether conv_wgrad evaluates the shape on the matrix pipe (fpcc_conv_wgrad_matrix: c_in % 32 == 0, c_out 32 | 64 | 128 | 256);
+    a host-side answer, the predicate the library's dispatch reads"""
+    return bool(lib().fpcc_conv_wgrad_matrix(int(c_in), int(c_out)))
 
 
 # ---------------------------------------------------------------------------------------------------------------

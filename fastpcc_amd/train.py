@@ -271,14 +271,14 @@ def ddp_bench(trainer: Trainer, data: Iterator[PCData], steps: int, warmup: int,
     return elapsed_max, total_voxels, comm_ms, last
 
 
-V2_MODELS = ('baseline_r1', 'baseline_r3', 'baseline_r5')
+V2_MODELS = ('baseline_r1', 'baseline_r3', 'baseline_r5', 'expanded_r3', 'expanded_r5')
 
 
 def ddp_training_record(steps: int, warmup: int, device: torch.device, resolution: int = 128,
                         cfg: Optional[TrainConfig] = None, model_name: str = 'baseline_r1') -> Optional[dict]:
     """cfg#5 on the ranks of the EXISTING process group (bench.py --gpus N calls this after its replica timing, so the
-    driver's own scaling command produces the DDP figure too): lossy_coord_v2/baseline_r1, global batch 8 split 8 / N per
-    rank, gradients all-reduced over RCCL by DDP.  Collective; rank 0 returns the record, other ranks None."""
+    driver's own scaling command produces the DDP figure too): lossy_coord_v2/<model_name> (one of V2_MODELS: baseline_r1 | r3 | r5,
+    expanded_r3 | r5 -- the pyramid widened to 256 channels), global batch 8 split 8 / N per rank, gradients all-reduced over RCCL by DDP.  Collective; rank 0 returns the record, other ranks None."""
     from .codecs.lossy_coord_v2 import Model
     from .codecs.lossy_coord_v2 import model_config
     if model_name not in V2_MODELS:
@@ -324,7 +324,7 @@ def ddp_training_record(steps: int, warmup: int, device: torch.device, resolutio
 
 def bench(steps: int, warmup: int, gpus: int, resolution: int = 128, cfg: Optional[TrainConfig] = None,
           model_name: str = 'baseline_r1', *, amp_dtype: str = '') -> Optional[dict]:
-    """times `steps` optimisation steps of lossy_coord_v2/<model_name> (baseline_r1 | r3 | r5) on synthetic ShapeNet-like batches;
+    """times `steps` optimisation steps of lossy_coord_v2/<model_name> (baseline_r1 | r3 | r5, expanded_r3 | r5) on synthetic ShapeNet-like batches;
     rank 0 returns the result record, other ranks None.  amp_dtype ('' | 'bfloat16') overrides cfg.amp_dtype when given"""
     cfg = cfg or TrainConfig()
     if amp_dtype:

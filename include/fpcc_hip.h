@@ -435,6 +435,12 @@ int fpcc_conv_wgrad_f32(const float *x, int c_in, int ldx, const float *dy, int 
                         const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
                         const int32_t *out_map, int64_t om_os, int64_t om_gs, int groups, int64_t n,
                         const int32_t *row_order, float *dw, int accumulate, void *ws, int64_t ws_bytes, void *stream);
+/* 1 when fpcc_conv_wgrad_f32 evaluates the shape on the matrix pipe (v_mfma_f32_32x32x2_f32, fp32 throughout): c_in a multiple of
+ * 32 and c_out 32 | 64 | 128 | 256; 0: the small-shape or VALU kernels.  The predicate the dispatch itself reads.  The row splits
+ * are a function of (c_in, n_offsets * groups, n) and never of c_out, and every element of dw is one chain over the same row walk,
+ * so dw[..., :128] and dw[..., 128:] of a 256-column call are bit for bit the results of two 128-column calls on dy[:, :128] and
+ * dy[:, 128:] (ldy = 256). */
+int fpcc_conv_wgrad_matrix(int c_in, int c_out);
 /* Kernel of the input-gradient convolution: wt[k][co][ci] = w[flip ? n_offsets-1-k : k][ci][co] (fastpcc_amd/autograd.py). */
 int fpcc_transpose_weights_f32(const float *w, int n_offsets, int c_in, int c_out, int flip, float *wt, void *stream);
 /* row_order (NULL = none): the neighbour-pattern permutation of fpcc_conv_row_keys for this nbr table.  Multi-offset maps are
