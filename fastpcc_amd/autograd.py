@@ -18,7 +18,8 @@ Mixed precision (`conv_autocast(torch.bfloat16)`): the same three products with 
 (fpcc_conv_bf16 / fpcc_conv_wgrad_bf16), fp32 accumulation, fp32 results.  The forward casts x once and saves the bf16 copy, which
 the weight gradient reuses; the backward casts dy once for both gradient products; weights are packed from the fp32 parameters per
 call.  The choice is made by the forward and travels with the saved tensors -- autograd runs the backward on its own thread, where
-the thread-local context is not set.  Shapes outside fpcc_conv_bf16_supported, and kind 'tab', keep the fp32 code as it is.
+the thread-local context is not set.  Shapes outside fpcc_conv_bf16_supported and fpcc_conv_bf16_wide_supported (the layers that write
+256 channels), and kind 'tab', keep the fp32 code as it is.
 """
 import contextlib
 import threading
@@ -45,6 +46,10 @@ class ConvSpec:
 import os as _os
 PACK = 'fresh' if _os.environ.get('FPCC_TRAIN_PACK', 'off') in ('fresh', '1') else False
 
+
+# 256 columns per launch of an input gradient whose width is a multiple of 256 (else 128): same bits, kept by time
+# (profiles/r11/expanded_amp.md)
+WIDE_INPUT_GRAD = True
 
 _amp = threading.local()
 
@@ -78,18 +83,38 @@ def _bf16_forward_ok(c_in: int, c_out: int, kind: str) -> bool:
     """the calling thread asked for bfloat16 and the forward (hence the weight gradient) of this layer has a bf16 kernel"""
     if compute_dtype() is not torch.bfloat16 or kind not in _KIND_SHAPE:
         return False
-    return ops.conv_bf16_supported(c_in, c_out, *_KIND_SHAPE[kind])
+    return _bf16_shape_ok(c_in, c_out, *_KIND_SHAPE[kind])
+
+
+def _bf16_shape_ok(c_in: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
+    """training routes the shape to the bf16 entries: up to 128 columns, or the 256 columns of the expanded rate points"""
+    return ops.conv_bf16_supported(c_in, c_out, n_offsets, groups) or ops.conv_bf16_wide_supported(c_in, c_out, n_offsets, groups)
+
+
+def _mirrored(c_out: int, kind: str):
+    """(c_in, n_offsets, groups) of the convolution that is the layer's input gradient, or None"""
+    if kind == 'gen':                     # one packed GEMM [m, 8 c_out] @ [8 c_out, c_in]
+        return (8 * c_out, 1, 1) if c_out % 16 == 0 else None
+    return (c_out,) + {'k1': (1, 1), 'k3': (27, 1), 'k2s2': (1, 8), 'k2s2T': (8, 1)}[kind]
+
+
+def _bf16_input_grad_step(c_in: int, c_out: int, kind: str) -> int:
+    """columns per launch of the layer's input gradient (a convolution c_out -> c_in on the mirrored maps) on the bf16 kernels:
+    256 where c_in is a multiple of 256 and the mirrored shape is a routed 256-column one, else 128 (or all of a narrower c_in);
+    0: no bf16 kernel.  The bits do not depend on the step (fpcc_hip.h), so it is chosen by time alone"""
+    m = _mirrored(c_out, kind)
+    if m is None or (c_in > 128 and c_in % 128):
+        return 0
+    width = min(c_in, 128)
+    if not ops.conv_bf16_supported(m[0], width, m[1], m[2]):
+        return 0
+    # (the wide step only replaces 128-column steps: a shape kept on fp32 at 128 columns stays there)
+    return 256 if WIDE_INPUT_GRAD and c_in % 256 == 0 and ops.conv_bf16_wide_supported(m[0], 256, m[1], m[2]) else width
 
 
 def _bf16_input_grad_ok(c_in: int, c_out: int, kind: str) -> bool:
-    """the input gradient of the layer (a convolution c_out -> c_in on the mirrored maps, 128 columns per launch) has a bf16 kernel"""
-    if c_in > 128 and c_in % 128:
-        return False
-    width = min(c_in, 128)
-    if kind == 'gen':                     # one packed GEMM [m, 8 c_out] @ [8 c_out, c_in]
-        return c_out % 16 == 0 and ops.conv_bf16_supported(8 * c_out, width, 1, 1)
-    n_offsets, groups = {'k1': (1, 1), 'k3': (27, 1), 'k2s2': (1, 8), 'k2s2T': (8, 1)}[kind]
-    return ops.conv_bf16_supported(c_out, width, n_offsets, groups)
+    """the input gradient of the layer has a bf16 kernel"""
+    return _bf16_input_grad_step(c_in, c_out, kind) > 0
 
 
 def _forward_bf16(x: torch.Tensor, w: torch.Tensor, s: ConvSpec, **epilogue) -> torch.Tensor:
@@ -108,37 +133,40 @@ def _forward_bf16(x: torch.Tensor, w: torch.Tensor, s: ConvSpec, **epilogue) -> 
     return ops.conv_bf16(x, wp, c_out, s.n_in, groups=8, **epilogue)                                     # 'gen'
 
 
-def _wide_bf16(call, pack, width: int, rows: int, device) -> torch.Tensor:
-    """_wide for the bf16 kernels: `pack(lo, cols)` packs columns lo .. lo + cols of the gradient weights straight from the parameter"""
-    if width <= 128:
+def _wide_bf16(call, pack, width: int, rows: int, device, step: int = 128) -> torch.Tensor:
+    """_wide for the bf16 kernels: `pack(lo, cols)` packs columns lo .. lo + cols of the gradient weights straight from the parameter;
+    `step` columns per launch (_bf16_input_grad_step)"""
+    if width <= step:
         return call(pack(0, width), width, None)
     out = torch.empty((rows, width), dtype=torch.float32, device=device)
-    for lo in range(0, width, 128):
-        call(pack(lo, 128), 128, out[:, lo: lo + 128])
+    for lo in range(0, width, step):
+        call(pack(lo, step), step, out[:, lo: lo + step])
     return out
 
 
 def _input_grad_bf16(dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
     """_input_grad on a bfloat16 dy: the mirrored convolution with W'[k] = W[mirror(k)]^T packed straight from W"""
     c_in, c_out = w.shape[-2], w.shape[-1]
+    step = _bf16_input_grad_step(c_in, c_out, s.kind)
     if s.kind == 'k1':
         return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, out=out),
                           lambda lo, c: ops.pack_weights_bf16(w, 1, c_out, c, transpose=True, src_width=c_in, src_off=lo),
-                          c_in, s.n_in, dy.device)
+                          c_in, s.n_in, dy.device, step)
     if s.kind == 'k3':
         return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, nbr=s.table, n_offsets=27, nbr_ks=s.n_in, nbr_os=1,
                                                            row_order=s.row_order, out=out),
                           lambda lo, c: ops.pack_weights_bf16(w, 27, c_out, c, transpose=True, flip=True, src_width=c_in, src_off=lo),
-                          c_in, s.n_in, dy.device)
+                          c_in, s.n_in, dy.device, step)
     pack8 = lambda lo, c: ops.pack_weights_bf16(w, 8, c_out, c, transpose=True, src_width=c_in, src_off=lo)      # noqa: E731
     if s.kind == 'k2s2':
         return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_out, groups=8, out_map=s.table, om_os=8, om_gs=1,
-                                                           out_rows=s.n_in, out=out), pack8, c_in, s.n_in, dy.device)
+                                                           out_rows=s.n_in, out=out), pack8, c_in, s.n_in, dy.device, step)
     if s.kind == 'k2s2T':
         return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy, wp, c, s.n_in, nbr=s.table, n_offsets=8, nbr_ks=1, nbr_os=8, out=out),
-                          pack8, c_in, s.n_in, dy.device)
+                          pack8, c_in, s.n_in, dy.device, step)
     # 'gen': dY [8m, c_out] read as [m, 8 c_out]; the eight packed images W[g]^T side by side ARE the image of [8 c_out, c_in]
-    return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy.view(s.n_in, 8 * c_out), wp, c, s.n_in, out=out), pack8, c_in, s.n_in, dy.device)
+    return _wide_bf16(lambda wp, c, out: ops.conv_bf16(dy.view(s.n_in, 8 * c_out), wp, c, s.n_in, out=out), pack8, c_in, s.n_in, dy.device,
+                      step)
 
 
 def _weight_grad_bf16(x: torch.Tensor, dy: torch.Tensor, w: torch.Tensor, s: ConvSpec) -> torch.Tensor:
@@ -429,15 +457,19 @@ class LinearActFn(torch.autograd.Function):
             gb = ops.cast_bf16(g)
             wd = weight.detach().contiguous()
             if ctx.needs_input_grad[0]:
-                if _bf16_input_grad_ok(c_in, c_out, 'k1'):         # B[co][ci] = weight[co][ci]: the stored layout, 128 columns a launch
+                step = _bf16_input_grad_step(c_in, c_out, 'k1')
+                if step:                                            # B[co][ci] = weight[co][ci]: the stored layout, `step` columns a launch
                     dx = _wide_bf16(lambda wp, c, out: ops.conv_bf16(gb, wp, c, n, out=out),
-                                    lambda lo, c: ops.pack_weights_bf16(wd, 1, c_out, c, src_width=c_in, src_off=lo), c_in, n, dy.device)
+                                    lambda lo, c: ops.pack_weights_bf16(wd, 1, c_out, c, src_width=c_in, src_off=lo), c_in, n, dy.device,
+                                    step)
                 else:
                     dx = _wide(lambda wt, c, out: ops.conv_f32(g, wt, c, n, out=out, pack=PACK), wd, c_in, n, dy.device)
             if ctx.needs_input_grad[1]:
                 if ops.conv_bf16_supported(c_out, c_in):            # dW [c_out, c_in] = g^T x, the stored orientation
                     dw = ops.conv_wgrad_bf16(gb, x, n).view(c_out, c_in)
-                else:
+                else:       # its own orientation, the shape one of the two queries accepted for the forward (256 -> 256, 512 -> 256:
+                    #         the 256-column weight gradient), transposed as a view
+                    assert _bf16_shape_ok(c_in, c_out)
                     dw = ops.conv_wgrad_bf16(x, gb, n).view(c_in, c_out).t()
         elif ctx.needs_input_grad[0]:
             dx = _wide(lambda wt, c, out: ops.conv_f32(g, wt, c, n, out=out, pack=PACK), weight.detach(), c_in, n, dy.device)

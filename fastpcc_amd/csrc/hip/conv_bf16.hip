@@ -3,7 +3,8 @@
 //
 //   k_cast_bf16          fp32 rows -> bf16 rows (round to nearest even), 16-byte stores
 //   k_pack_weights_bf16  fp32 master weights -> the B-operand image of the 32x32x16 MFMA (optionally transposed / mirrored)
-//   k_conv_bf16          output-stationary forward: a wave owns 32 output rows x all column blocks, A gathered straight to registers
+//   k_conv_bf16          output-stationary forward: a wave owns 32 output rows x all column blocks (256 columns: x one column half),
+//                        A gathered straight to registers
 //   k_wgrad_bf16         weight gradient: the MFMA K dimension is the row index, both operands transposed through LDS
 //
 // Operand lane maps of the 32x32x16 bf16 MFMA (lane l, r = l & 31, h = l >> 5, element j = 0..7):
@@ -87,16 +88,18 @@ struct ConvBf16Args {
 };
 
 // One chain: acc += sum over offsets k0 <= k < k1 (ascending) and 16-channel steps (ascending) of A(k) B(g, k) for the wave's 32 rows;
-// o = the lane's output row (-1: none).  An offset none of the rows has is skipped (it would add zeros).
-template <int NB>
-__device__ __forceinline__ void chain_bf16(const ConvBf16Args &a, f32x16 (&acc)[NB], int k0, int k1, int g, int64_t o, int lane) {
+// o = the lane's output row (-1: none).  An offset none of the rows has is skipped (it would add zeros).  The weights image is NBW
+// column blocks wide and the chain takes the NB blocks from nb0 on: an element's chain does not depend on the block it sits in.
+template <int NB, int NBW = NB>
+__device__ __forceinline__ void chain_bf16(const ConvBf16Args &a, f32x16 (&acc)[NB], int k0, int k1, int g, int64_t o, int lane,
+                                           int nb0 = 0) {
     const int h = lane >> 5, ks = a.c_in / 16;
     for (int k = k0; k < k1; ++k) {
         int64_t in = -1;
         if (o >= 0) in = a.nbr ? (int64_t)a.nbr[k * a.nbr_ks + o * a.nbr_os] : o;
         if (__ballot(in >= 0) == 0) continue;
         const bf16x8 *xa = reinterpret_cast<const bf16x8 *>(a.x + (in >= 0 ? in : 0) * a.ldx + 8 * h);
-        const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(a.wp) + ((int64_t)(g * a.n_off + k) * ks * NB) * 64 + lane;
+        const bf16x8 *wb = reinterpret_cast<const bf16x8 *>(a.wp) + ((int64_t)(g * a.n_off + k) * ks * NBW + nb0) * 64 + lane;
         for (int s = 0; s < ks; s += 2) {           // c_in % 32 == 0: two K steps per turn, their loads issued together
             bf16x8 av0 = {0, 0, 0, 0, 0, 0, 0, 0}, av1 = av0;
             if (in >= 0) {
@@ -105,7 +108,7 @@ __device__ __forceinline__ void chain_bf16(const ConvBf16Args &a, f32x16 (&acc)[
             }
             bf16x8 bv[2 * NB];
 #pragma unroll
-            for (int i = 0; i < 2 * NB; ++i) bv[i] = wb[(int64_t)(s * NB + i) * 64];
+            for (int i = 0; i < 2 * NB; ++i) bv[i] = wb[(int64_t)(NBW == NB ? s * NB + i : (s + i / NB) * NBW + i % NB) * 64];
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av0, bv[nb], acc[nb], 0, 0, 0);
 #pragma unroll
@@ -129,9 +132,12 @@ __device__ __forceinline__ void clear_acc(f32x16 (&acc)[NB]) {
 //          sums from LDS: four times the loads in flight per row block -- a lone wave walks 27 offsets x C_in / 32 turns of dependent
 //          loads, which on the small maps of a pyramid (tens to thousands of rows) is all the time there is;  grid (ceil(n_out / 32), groups)
 //   else   a wave owns 32 output rows;  grid (ceil(n_out / 128), groups), one row block per wave
-template <int NB, bool SPLIT>
+//   NBW > NB (256 columns as two column halves of the 128-column geometry): blockIdx.z is the half, which moves the window of the
+//          weights image and the output columns and nothing else
+template <int NB, bool SPLIT, int NBW = NB>
 __global__ __launch_bounds__(256) void k_conv_bf16(ConvBf16Args a) {
     __shared__ float s_part[SPLIT ? 3 * NB * 16 * 64 : 1];
+    const int nb0 = NBW == NB ? 0 : NB * (int)blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const int64_t pos = (SPLIT ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave) * 32 + r;
     const int g = blockIdx.y;
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(256) void k_conv_bf16(ConvBf16Args a) {
     f32x16 acc[NB];
     clear_acc<NB>(acc);
     if (SPLIT) {
-        chain_bf16<NB>(a, acc, offset_group_begin(wave, a.n_off), offset_group_begin(wave + 1, a.n_off), g, o, lane);
+        chain_bf16<NB, NBW>(a, acc, offset_group_begin(wave, a.n_off), offset_group_begin(wave + 1, a.n_off), g, o, lane, nb0);
         if (wave > 0) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb)
@@ -160,7 +166,7 @@ __global__ __launch_bounds__(256) void k_conv_bf16(ConvBf16Args a) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[nb][i] = acc[nb][i] + s_part[((w * NB + nb) * 16 + i) * 64 + lane];
     } else {
-        chain_bf16<NB>(a, acc, 0, a.n_off, g, o, lane);
+        chain_bf16<NB, NBW>(a, acc, 0, a.n_off, g, o, lane, nb0);
     }
 
     const float slope = a.act == FPCC_ACT_PRELU ? a.slope[0] : 0.0f;
@@ -172,10 +178,20 @@ __global__ __launch_bounds__(256) void k_conv_bf16(ConvBf16Args a) {
         if (d < 0) continue;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            const int col = 32 * nb + r;
+            const int col = 32 * (nb0 + nb) + r;
             a.out[d * a.ldo + col] = finish(acc[nb][i], a.bias ? a.bias[col] : 0.0f, a.act, slope, a.clip);
         }
     }
+}
+
+// 256 columns: the column halves on grid.z.  Measured against one unit of eight column blocks per wave (k_conv_bf16<8, SPLIT>: the A
+// fragment gathered once, 246 + 144 registers, one wave per SIMD), the halves were 1.4 to 1.9 times faster on every map of the
+// expanded_r3 step (profiles/r11/expanded_amp.md); the unit is not built.
+void launch_conv_bf16_256(const ConvBf16Args &a, hipStream_t s) {
+    if (a.n_off >= 8)
+        hipLaunchKernelGGL((k_conv_bf16<4, true, 8>), dim3(blocks_for(a.n_out, 32), a.groups, 2), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL((k_conv_bf16<4, false, 8>), dim3(blocks_for(a.n_out, 128), a.groups, 2), dim3(256), 0, s, a);
 }
 
 template <int NB>
@@ -320,9 +336,16 @@ int wgrad_bf16_splits(int c_in, int kg, int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(want, 512));
 }
 
-bool shape_ok(int c_in, int c_out, int n_offsets, int groups) {
-    return c_in >= 32 && c_in % 32 == 0 && (c_out == 32 || c_out == 64 || c_out == 128) && n_offsets >= 1 && n_offsets <= 32 &&
-           groups >= 1 && groups <= 8;
+bool maps_ok(int c_in, int n_offsets, int groups) {
+    return c_in >= 32 && c_in % 32 == 0 && n_offsets >= 1 && n_offsets <= 32 && groups >= 1 && groups <= 8;
+}
+
+bool shape_ok(int c_in, int c_out, int n_offsets, int groups) {          // the shapes fpcc_conv_bf16_supported is asked about
+    return maps_ok(c_in, n_offsets, groups) && (c_out == 32 || c_out == 64 || c_out == 128);
+}
+
+bool entry_ok(int c_in, int c_out, int n_offsets, int groups) {          // the shapes the entries take
+    return maps_ok(c_in, n_offsets, groups) && (c_out == 32 || c_out == 64 || c_out == 128 || c_out == 256);
 }
 
 }  // namespace
@@ -336,6 +359,12 @@ extern "C" int fpcc_conv_bf16_supported(int c_in, int c_out, int n_offsets, int 
     if (!shape_ok(c_in, c_out, n_offsets, groups)) return 0;
     if (n_offsets == 1 && groups == 1 && c_in == 64 && c_out == 128) return 0;
     return 1;
+}
+
+// The 256-column shapes training routes here (the layers of the expanded rate points that write 256 channels): all the entries take --
+// the keep rule that removed 64 -> 128 above removed none of them (profiles/r11/expanded_amp.md).
+extern "C" int fpcc_conv_bf16_wide_supported(int c_in, int c_out, int n_offsets, int groups) {
+    return c_out == 256 && maps_ok(c_in, n_offsets, groups) ? 1 : 0;
 }
 
 extern "C" int fpcc_cast_f32_bf16(const float *src, int64_t ld, int64_t n, int c, uint16_t *dst, int64_t ldd, void *stream) {
@@ -367,7 +396,7 @@ extern "C" int fpcc_conv_bf16(const uint16_t *x, int c_in, int ldx, const int32_
                               void *stream) {
     (void)ws;
     (void)ws_bytes;
-    if (!shape_ok(c_in, c_out, n_offsets, groups)) return fail_arg("conv_bf16: c_in % 32 == 0, c_out in {32, 64, 128}, 1..32 offsets, 1..8 groups");
+    if (!entry_ok(c_in, c_out, n_offsets, groups)) return fail_arg("conv_bf16: c_in % 32 == 0, c_out in {32, 64, 128, 256}, 1..32 offsets, 1..8 groups");
     if (n_out < 0 || n_out > (int64_t(1) << 31) - 256) return fail_arg("conv_bf16: n_out out of range");
     if (n_out == 0) return FPCC_OK;               // (an empty map's table may be a null pointer)
     if (!nbr && n_offsets != 1) return fail_arg("conv_bf16: identity map needs n_offsets == 1");
@@ -378,14 +407,15 @@ extern "C" int fpcc_conv_bf16(const uint16_t *x, int c_in, int ldx, const int32_
     ConvBf16Args a{x, c_in, ldx, nbr, n_offsets, nbr_ks, nbr_os, w_packed, bias, c_out, groups, out_map, om_os, om_gs, out, ldo, n_out,
                    act, slope, clip, row_order};
     hipStream_t s = as_stream(stream);
-    if (c_out == 128) launch_conv_bf16<4>(a, s);
+    if (c_out == 256) launch_conv_bf16_256(a, s);
+    else if (c_out == 128) launch_conv_bf16<4>(a, s);
     else if (c_out == 64) launch_conv_bf16<2>(a, s);
     else launch_conv_bf16<1>(a, s);
     return check_hip(hipGetLastError(), "k_conv_bf16");
 }
 
 extern "C" int64_t fpcc_conv_wgrad_bf16_ws_bytes(int c_in, int c_out, int n_offsets, int groups, int64_t n) {
-    if (!shape_ok(c_in, c_out, n_offsets, groups) || n < 0) return FPCC_E_ARG;
+    if (!entry_ok(c_in, c_out, n_offsets, groups) || n < 0) return FPCC_E_ARG;
     const int kg = n_offsets * groups;
     return (int64_t)wgrad_bf16_splits(c_in, kg, n) * kg * c_in * c_out * 4;
 }
@@ -394,7 +424,7 @@ extern "C" int fpcc_conv_wgrad_bf16(const uint16_t *x, int c_in, int ldx, const 
                                     const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
                                     const int32_t *out_map, int64_t om_os, int64_t om_gs, int groups, int64_t n,
                                     const int32_t *row_order, float *dw, int accumulate, void *ws, int64_t ws_bytes, void *stream) {
-    if (!shape_ok(c_in, c_out, n_offsets, groups)) return fail_arg("conv_wgrad_bf16: c_in % 32 == 0, c_out in {32, 64, 128}, 1..32 offsets, 1..8 groups");
+    if (!entry_ok(c_in, c_out, n_offsets, groups)) return fail_arg("conv_wgrad_bf16: c_in % 32 == 0, c_out in {32, 64, 128, 256}, 1..32 offsets, 1..8 groups");
     if (n < 0 || !dw) return fail_arg("conv_wgrad_bf16: sizes out of range or null dw");
     const int kg = n_offsets * groups;
     const int64_t count = (int64_t)kg * c_in * c_out;
@@ -412,7 +442,8 @@ extern "C" int fpcc_conv_wgrad_bf16(const uint16_t *x, int c_in, int ldx, const 
     WgradBf16Args a{x, c_in, ldx, dy, c_out, ldy, nbr, n_offsets, nbr_ks, nbr_os, out_map, om_os, om_gs, groups, n, row_order,
                     rows_per_split, static_cast<float *>(ws)};
     const dim3 grid(splits, kg, (c_in + 63) / 64);
-    if (c_out == 128) hipLaunchKernelGGL((k_wgrad_bf16<4>), grid, dim3(256), 0, s, a);
+    if (c_out == 256) hipLaunchKernelGGL((k_wgrad_bf16<8>), grid, dim3(256), 0, s, a);
+    else if (c_out == 128) hipLaunchKernelGGL((k_wgrad_bf16<4>), grid, dim3(256), 0, s, a);
     else if (c_out == 64) hipLaunchKernelGGL((k_wgrad_bf16<2>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_wgrad_bf16<1>), grid, dim3(256), 0, s, a);
     if (int rc = check_hip(hipGetLastError(), "k_wgrad_bf16")) return rc;

@@ -132,6 +132,7 @@ _SIGS = {
     'fpcc_int_level_expand': (_i64, [_vp, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_octree_children': (_i64, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_conv_bf16_supported': (_i32, [_i32, _i32, _i32, _i32]),
+    'fpcc_conv_bf16_wide_supported': (_i32, [_i32, _i32, _i32, _i32]),
     'fpcc_cast_f32_bf16': (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
     'fpcc_conv_pack_weights_bf16': (_i32, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     'fpcc_conv_bf16': (_i32, [_vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _i64, _vp, _i32, _i64, _i32,
@@ -1035,8 +1036,14 @@ def conv_wgrad_matrix(c_in: int, c_out: int) -> bool:
 
 @functools.lru_cache(maxsize=None)
 def conv_bf16_supported(c_in: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
-    """shapes fpcc_conv_bf16 / fpcc_conv_wgrad_bf16 take; every other shape stays on the fp32 kernels"""
+    """shapes of up to 128 columns training routes to fpcc_conv_bf16 / fpcc_conv_wgrad_bf16"""
     return bool(lib().fpcc_conv_bf16_supported(int(c_in), int(c_out), int(n_offsets), int(groups)))
+
+
+@functools.lru_cache(maxsize=None)
+def conv_bf16_wide_supported(c_in: int, c_out: int, n_offsets: int = 1, groups: int = 1) -> bool:
+    """the 256-column shapes training routes to them (the expanded rate points); False for every c_out != 256"""
+    return bool(lib().fpcc_conv_bf16_wide_supported(int(c_in), int(c_out), int(n_offsets), int(groups)))
 
 
 def _rows2d_bf16(t: torch.Tensor, name: str):

@@ -822,10 +822,19 @@ int fpcc_simple_dec_pop_dev(int32_t *state, const uint8_t *stream, int64_t strea
  * order); no atomics, so the same call gives the same bits twice.  These bits are NOT those of
  * the fp32 entries and are not part of any stream format.  bf16 values travel as uint16_t (the upper half of the fp32 pattern).
  *
- * The entries take c_in a multiple of 32, c_out in {32, 64, 128}, 1 <= n_offsets <= 32, 1 <= groups <= 8.
+ * The column block an element sits in does not enter its order: the column halves of a 256-column forward are bit for bit the two
+ * 128-column calls on weights packed from the column windows src_off = 0 | 128, and the row walk and the number of row splits of the
+ * weight gradient are functions of (c_in, n_offsets * groups, n) alone, so the column halves of a 256-column weight gradient are bit
+ * for bit the two 128-column calls on dy[:, :128] and dy[:, 128:].
+ *
+ * The entries take c_in a multiple of 32, c_out in {32, 64, 128, 256}, 1 <= n_offsets <= 32, 1 <= groups <= 8.
  * fpcc_conv_bf16_supported: 1 for the shapes training ROUTES to them -- those, less the shapes measured no faster than the fp32 entries
  * on the maps of a training step (the per-point layer 64 -> 128; profiles/r07/amp_bf16.md) -- else 0: every other shape stays fp32. */
 int fpcc_conv_bf16_supported(int c_in, int c_out, int n_offsets, int groups);
+/* The same question for the 256-column shapes (the layers of the expanded rate points that write 256 channels): 1 for c_out == 256
+ * and a shape the entries take, less whatever was measured no faster than fp32 (nothing so far; profiles/r11/expanded_amp.md), 0 for
+ * everything else, every c_out != 256 included.  fpcc_conv_bf16_supported keeps its answers: 0 for c_out == 256. */
+int fpcc_conv_bf16_wide_supported(int c_in, int c_out, int n_offsets, int groups);
 /* dst[r][0..c) = bf16(src[r][0..c)), r < n.  c a multiple of 8; ld (floats) a multiple of 4, ldd (bf16) of 8; both pointers 16-byte
  * aligned.  A tensor is converted once per use as an operand, not once per gathered row. */
 int fpcc_cast_f32_bf16(const float *src, int64_t ld, int64_t n, int c, uint16_t *dst, int64_t ldd, void *stream);
@@ -841,7 +850,7 @@ int fpcc_conv_pack_weights_bf16(const float *w, int64_t n_mats, int c_in, int c_
                                 int src_off, uint16_t *w_packed, void *stream);
 /* fpcc_conv_f32 on bf16 rows x [*, c_in] (row stride ldx bf16, a multiple of 8) and packed weights of groups * n_offsets matrices;
  * nbr / out_map / row_order / bias / act / slope / clip as there, out fp32.  Output-stationary: a wave owns 32 output rows and all
- * column blocks and gathers its A operand straight to registers (16 bytes of a neighbour's row per 16-channel step); a block of 32
+ * column blocks (c_out == 256: the four blocks of one column half, the half on the grid) and gathers its A operand straight to registers (16 bytes of a neighbour's row per 16-channel step); a block of 32
  * rows none of which has an offset skips it.  The four offset groups of a layer of 8 or more offsets go to the four waves of a workgroup
  * and are added from LDS in that fixed order.  ws is not used (NULL, 0). */
 int fpcc_conv_bf16(const uint16_t *x, int c_in, int ldx, const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
