@@ -669,6 +669,18 @@ def _traced_launch(trace: list, fn, call, info) -> None:
         trace.append((ev0, ev1, info))
 
 
+def _conv_out(out: Optional[torch.Tensor], out_rows: Optional[int], n_out: int, groups: int, c_out: int, om_os: int, device):
+    """the output of conv_f32 / conv_bf16, allocated unless given (out_rows rows, by default one per row and group), and checked
+    -> (out, its pointer, its row pitch, om_os with its default)"""
+    if out is None:
+        rows = out_rows if out_rows is not None else n_out * groups
+        out = torch.empty((rows, c_out), dtype=torch.float32, device=device)
+    po, co, ldo = _rows2d(out, 'out')
+    if co != c_out:
+        raise ValueError('output width mismatch')
+    return out, po, ldo, om_os if om_os else groups
+
+
 def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: Optional[torch.Tensor] = None,
              nbr: Optional[torch.Tensor] = None, n_offsets: int = 1, nbr_ks: int = 0, nbr_os: int = 1,
              bias: Optional[torch.Tensor] = None, groups: int = 1, out_map: Optional[torch.Tensor] = None,
@@ -686,14 +698,7 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
     if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous() or \
             w.numel() != groups * n_offsets * (c1 + c2) * c_out:
         raise ValueError(f'weights must be contiguous fp32 [{groups},{n_offsets},{c1 + c2},{c_out}], got {tuple(w.shape)}')
-    if out is None:
-        rows = out_rows if out_rows is not None else n_out * groups
-        out = torch.empty((rows, c_out), dtype=torch.float32, device=x1.device)
-    po, co, ldo = _rows2d(out, 'out')
-    if co != c_out:
-        raise ValueError('output width mismatch')
-    if om_os == 0:
-        om_os = groups
+    out, po, ldo, om_os = _conv_out(out, out_rows, n_out, groups, c_out, om_os, x1.device)
     ws, ws_bytes = None, 0
     wp = packed_weights(w, c1, c2, c_out, n_offsets, groups, fresh=(pack == 'fresh')) if pack else None
     if wp is None and n_out > 0:
@@ -1000,28 +1005,35 @@ def keys_member(keys: torch.Tensor, query: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch.Tensor] = None, n_offsets: int = 1,
-               nbr_ks: int = 0, nbr_os: int = 1, out_map: Optional[torch.Tensor] = None, om_os: int = 0, om_gs: int = 1,
-               groups: int = 1, out: Optional[torch.Tensor] = None, accumulate: bool = False,
-               row_order: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """dW [groups, n_offsets, c_in, c_out] of the convolution whose forward used these row maps; see fpcc_conv_wgrad_f32"""
-    px, c_in, ldx = _rows2d(x, 'x')
-    pd, c_out, ldy = _rows2d(dy, 'dy')
+def _conv_wgrad(rows2d, ws_bytes_entry: str, entry: str, x, dy, n, nbr, n_offsets, nbr_ks, nbr_os, out_map, om_os, om_gs, groups, out,
+                accumulate, row_order) -> torch.Tensor:
+    """conv_wgrad / conv_wgrad_bf16: `rows2d` checks the operands' dtype, the two entries are the workspace query and the launch"""
+    px, c_in, ldx = rows2d(x, 'x')
+    pd, c_out, ldy = rows2d(dy, 'dy')
     if out is None:
         out = torch.empty((groups, n_offsets, c_in, c_out), dtype=torch.float32, device=x.device)
         accumulate = False
     if not out.is_contiguous() or out.numel() != groups * n_offsets * c_in * c_out or out.dtype != torch.float32:
         raise ValueError('dw must be contiguous fp32 [groups, n_offsets, c_in, c_out]')
     L = lib()
-    need = _ok(L.fpcc_conv_wgrad_ws_bytes(c_in, c_out, n_offsets, groups, n))
+    need = _ok(getattr(L, ws_bytes_entry)(c_in, c_out, n_offsets, groups, n))
     ws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
     if om_os == 0:
         om_os = groups
-    _ok(L.fpcc_conv_wgrad_f32(px, c_in, ldx, pd, c_out, ldy, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os,
-                              _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs, groups, n,
-                              _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
-                              _stream()))
+    _ok(getattr(L, entry)(px, c_in, ldx, pd, c_out, ldy, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os,
+                          _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs, groups, n,
+                          _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
+                          _stream()))
     return out
+
+
+def conv_wgrad(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch.Tensor] = None, n_offsets: int = 1,
+               nbr_ks: int = 0, nbr_os: int = 1, out_map: Optional[torch.Tensor] = None, om_os: int = 0, om_gs: int = 1,
+               groups: int = 1, out: Optional[torch.Tensor] = None, accumulate: bool = False,
+               row_order: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW [groups, n_offsets, c_in, c_out] of the convolution whose forward used these row maps; see fpcc_conv_wgrad_f32"""
+    return _conv_wgrad(_rows2d, 'fpcc_conv_wgrad_ws_bytes', 'fpcc_conv_wgrad_f32', x, dy, n, nbr, n_offsets, nbr_ks, nbr_os, out_map,
+                       om_os, om_gs, groups, out, accumulate, row_order)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1086,14 +1098,7 @@ def conv_bf16(x: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out: int, *
     if w_packed.dtype != torch.bfloat16 or not w_packed.is_cuda or not w_packed.is_contiguous() or \
             w_packed.numel() != groups * n_offsets * c_in * c_out:
         raise ValueError(f'packed weights must hold {groups} x {n_offsets} x {c_in} x {c_out} bfloat16')
-    if out is None:
-        rows = out_rows if out_rows is not None else n_out * groups
-        out = torch.empty((rows, c_out), dtype=torch.float32, device=x.device)
-    po, co, ldo = _rows2d(out, 'out')
-    if co != c_out:
-        raise ValueError('output width mismatch')
-    if om_os == 0:
-        om_os = groups
+    out, po, ldo, om_os = _conv_out(out, out_rows, n_out, groups, c_out, om_os, x.device)
     _ok(lib().fpcc_conv_bf16(px, c_in, ldx, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os, w_packed.data_ptr(),
                              _dev(bias, torch.float32, 'bias', True), c_out, groups, _dev(out_map, torch.int32, 'out_map', True),
                              om_os, om_gs, po, ldo, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
@@ -1106,23 +1111,8 @@ def conv_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[
                     groups: int = 1, out: Optional[torch.Tensor] = None, accumulate: bool = False,
                     row_order: Optional[torch.Tensor] = None) -> torch.Tensor:
     """conv_wgrad on bfloat16 x and dy, dW fp32 [groups, n_offsets, c_in, c_out]; see fpcc_conv_wgrad_bf16"""
-    px, c_in, ldx = _rows2d_bf16(x, 'x')
-    pd, c_out, ldy = _rows2d_bf16(dy, 'dy')
-    if out is None:
-        out = torch.empty((groups, n_offsets, c_in, c_out), dtype=torch.float32, device=x.device)
-        accumulate = False
-    if not out.is_contiguous() or out.numel() != groups * n_offsets * c_in * c_out or out.dtype != torch.float32:
-        raise ValueError('dw must be contiguous fp32 [groups, n_offsets, c_in, c_out]')
-    L = lib()
-    need = _ok(L.fpcc_conv_wgrad_bf16_ws_bytes(c_in, c_out, n_offsets, groups, n))
-    ws = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
-    if om_os == 0:
-        om_os = groups
-    _ok(L.fpcc_conv_wgrad_bf16(px, c_in, ldx, pd, c_out, ldy, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os,
-                               _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs, groups, n,
-                               _dev(row_order, torch.int32, 'row_order', True), out.data_ptr(), int(accumulate), ws.data_ptr(), need,
-                               _stream()))
-    return out
+    return _conv_wgrad(_rows2d_bf16, 'fpcc_conv_wgrad_bf16_ws_bytes', 'fpcc_conv_wgrad_bf16', x, dy, n, nbr, n_offsets, nbr_ks, nbr_os,
+                       out_map, om_os, om_gs, groups, out, accumulate, row_order)
 
 
 def transpose_weights(w: torch.Tensor, n_offsets: int, c_in: int, c_out: int, flip: bool) -> torch.Tensor:
