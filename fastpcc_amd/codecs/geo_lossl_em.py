@@ -329,7 +329,7 @@ class GeoLosslessEntropyModel(nn.Module):
                     residual_job = ship_residuals()
                 if idx == last_coded and not self.evaluate_unused_tail:
                     break
-                lower = self.decoder_block[idx](res, fea_pred)
+                lower = self._decode_residual(idx, res, fea_pred, self._clip_symbol_range(idx, scale))
             else:
                 lower = self.decoder_block[idx](fea_pred)
             del fea_pred
@@ -412,6 +412,28 @@ class GeoLosslessEntropyModel(nn.Module):
             tm['enc_done'] = time.perf_counter()
         return out
 
+    def _clip_symbol_range(self, idx: int, scale: float):
+        """(lo, hi, scale) of the symbols level idx's residual block can produce -- its output is clamped to +-bound before it is
+        quantised --, or None when the block states no such bound"""
+        bound = getattr(self.residual_block[idx], '_bound', None)
+        if bound is None or not bound > 0:
+            return None
+        hi = int(math.ceil(float(bound) * scale))
+        return -hi, hi, scale
+
+    def _decode_residual(self, idx: int, res: torch.Tensor, fea_pred: ME.SparseTensor, sym_range):
+        """level idx's decoder block on the quantised residual `res` (k / scale for symbols k inside sym_range = (lo, hi, scale), or
+        None: not known) and the prediction"""
+        block = self.decoder_block[idx]
+        if sym_range is not None and getattr(block, 'takes_symbol_range', False):
+            # a stream's alphabet inside the range the encoder is clamped to: state that one, so that whatever the streams hold the
+            # block keeps ONE table (a table's rows do not depend on where it starts)
+            clip = self._clip_symbol_range(idx, sym_range[2])
+            if clip is not None and clip[0] <= sym_range[0] and sym_range[1] <= clip[1]:
+                sym_range = clip
+            return block(res, fea_pred, sym_range=sym_range)
+        return block(res, fea_pred)
+
     handover_retries = 0      # process-wide: coder-pool jobs that failed and succeeded when repeated after a synchronise
 
     # -- decompress -----------------------------------------------------------------------------------------------------
@@ -451,6 +473,8 @@ class GeoLosslessEntropyModel(nn.Module):
                 coord_bytes_list = BytesListUtils.split_bytes_list(None, n_streams, bs) if n_streams else []
                 bottom_xyz, _ = self.rans_decode_with_cdf(bs, 0, 3)
             parsed.append((bottom_level, bottom_rows, n_sym, sym_offset, sym_cdf, sym_payload, coord_bytes_list, bottom_xyz))
+        # every residual symbol lies in its stream's alphabet: [offset, offset + len(cdf) - 2]
+        sym_range = (min(p[3] for p in parsed), max(p[3] + len(p[4]) - 2 for p in parsed), scale)
         bottom_level = parsed[0][0]
         if any(p[0] != bottom_level for p in parsed):
             raise ValueError('the clouds of one traversal must share the depth of the pyramid')
@@ -530,7 +554,7 @@ class GeoLosslessEntropyModel(nn.Module):
                     fea_pred = self.hyper_decoder_fea[idx](lower, target_key)
                     if idx > self.skip_encoding_fea:
                         res = residuals([cur_map.n])
-                        lower = self.decoder_block[idx](res, fea_pred)
+                        lower = self._decode_residual(idx, res, fea_pred, sym_range)
                     else:
                         lower = self.decoder_block[idx](fea_pred)
                     continue
@@ -566,7 +590,7 @@ class GeoLosslessEntropyModel(nn.Module):
             if idx > self.skip_encoding_fea:
                 e = cm.batch_offsets(cur_map) if B > 1 else [0, cur_map.n]
                 res = residuals([e[c + 1] - e[c] for c in range(B)])
-                lower = self.decoder_block[idx](res, fea_pred)
+                lower = self._decode_residual(idx, res, fea_pred, sym_range)
             else:
                 lower = self.decoder_block[idx](fea_pred)
         if any(occupancy):

@@ -342,9 +342,13 @@ class SubDecoderGeoLossl(nn.Module):
         self.decoder = nn.Sequential(MEMLPBlock(out_ch + in_ch2, out_ch, act=act),
                                      MEMLPBlock(out_ch, out_ch, act=act))
 
-    def forward(self, x, y: ME.SparseTensor):
-        # inference: the four per-point layers and the concatenation as one launch (activations stay in LDS; same bits)
-        fused = mlp_chain_forward([*self.residual_decoder, *self.decoder], x, y, cat_layer=len(self.residual_decoder))
+    takes_symbol_range = True
+
+    def forward(self, x, y: ME.SparseTensor, sym_range=None):
+        # inference: the four per-point layers and the concatenation as one launch (activations stay in LDS; same bits).
+        # sym_range = (lo, hi, scale): x is a quantised residual, k / scale for integer symbols lo <= k <= hi
+        fused = mlp_chain_forward([*self.residual_decoder, *self.decoder], x, y, cat_layer=len(self.residual_decoder),
+                                  sym_range=sym_range)
         if fused is not None:
             return ME.SparseTensor(fused, coordinate_map_key=y.coordinate_map_key, coordinate_manager=y.coordinate_manager)
         if isinstance(x, torch.Tensor):

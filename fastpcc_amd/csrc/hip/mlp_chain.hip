@@ -253,6 +253,38 @@ __device__ __forceinline__ void load_b(f32x4 (&B)[G], const float *wp, int nbt, 
 // one MFMA layer on the workgroup's 64-row tile: A from `tin` (GT groups of 8 channels) and then from `ty` (GY groups), this
 // wave's column block `cb` of the output into `tout`.  NCB = column blocks of the layer (4: every wave does both row blocks;
 // 2: waves {w, w + 2} share a column block and take one row block each).
+// acc += A @ B over G groups of 8 channels: frag(g) = this lane's A fragment of group g, B[g] the wave's operand of that group.
+// A fragments three groups (12 MFMAs) ahead of their use; sched_barrier keeps them there (hipcc otherwise sinks every LDS read to
+// just before its first use and the wave waits out the LDS latency once per group)
+template <int G, typename F>
+__device__ __forceinline__ void wg_mfma(f32x16 &acc, F &&frag, const f32x4 (&B)[G]) {
+    f32x4 a0 = frag(0), a1 = frag(G > 1 ? 1 : 0), a2 = frag(G > 2 ? 2 : 0);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const f32x4 a3 = g + 3 < G ? frag(g + 3) : a0;
+        __builtin_amdgcn_sched_barrier(0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, B[g].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, B[g].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, B[g].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, B[g].w, acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        a0 = a1; a1 = a2; a2 = a3;
+    }
+}
+
+// bias / activation / clamp on the accumulators of row block `rb`, column block `cb`, into the tile `tout`
+__device__ __forceinline__ void wg_store(const f32x16 &acc, float *tout, int rb, int cb, float bias, int act, float slope, float clip,
+                                         int li, int lh) {
+    with_epilogue(act, clip, [&](auto act_c, auto clip_c) {
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int r = 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+            tout[r * kPitch + 32 * cb + li] = finish_t<decltype(act_c)::value, decltype(clip_c)::value>(acc[reg], bias, slope, clip);
+        }
+    });
+}
+
 template <int GT, int GY, int NCB>
 __device__ __forceinline__ void wg_layer(const float *tin, const float *ty, float *tout, const f32x4 (&B)[GT + GY], float bias, int act,
                                          float slope, float clip, int wv, int li, int lh) {
@@ -267,28 +299,8 @@ __device__ __forceinline__ void wg_layer(const float *tin, const float *ty, floa
         f32x16 acc;
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        // A fragments three groups (12 MFMAs) ahead of their use; sched_barrier keeps them there (hipcc otherwise sinks every LDS
-        // read to just before its first use and the wave -- alone on its SIMD -- waits out the LDS latency once per group)
-        f32x4 a0 = frag(0), a1 = frag(G > 1 ? 1 : 0), a2 = frag(G > 2 ? 2 : 0);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            const f32x4 a3 = g + 3 < G ? frag(g + 3) : a0;
-            __builtin_amdgcn_sched_barrier(0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.x, B[g].x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.y, B[g].y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.z, B[g].z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0.w, B[g].w, acc, 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            a0 = a1; a1 = a2; a2 = a3;
-        }
-        with_epilogue(act, clip, [&](auto act_c, auto clip_c) {
-#pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int r = 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-                tout[r * kPitch + 32 * cb + li] = finish_t<decltype(act_c)::value, decltype(clip_c)::value>(acc[reg], bias, slope, clip);
-            }
-        });
+        wg_mfma<G>(acc, frag, B);
+        wg_store(acc, tout, rb, cb, bias, act, slope, clip, li, lh);
     }
 }
 
@@ -300,6 +312,20 @@ __device__ __forceinline__ void stage_load(f32x4 (&v)[C / 16], const float *src,
     for (int k = 0; k < C / 16; ++k) {
         const int idx = t + 256 * k, r = idx / Q, c4 = idx - r * Q;
         v[k] = row0 + r < n ? *reinterpret_cast<const f32x4 *>(src + (row0 + r) * ld + 4 * c4) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+
+// stage_load with one per-thread address and wave-uniform steps from it (k_mlp_chain_a_lut has no registers to keep stage_load's
+// C / 16 row offsets, which hipcc hoists out of the tile loop, alive across the loop)
+template <int C>
+__device__ __forceinline__ void stage_load_stepped(f32x4 (&v)[C / 16], const float *src, int ld, int64_t row0, int64_t n, int t) {
+    constexpr int Q = C / 4, RS = 256 / Q;         // float4 per row, rows per step
+    const int r = t / Q, c4 = t - r * Q;
+    const float *p = src + (row0 + r) * ld + 4 * c4;
+#pragma unroll
+    for (int k = 0; k < C / 16; ++k) {
+        v[k] = row0 + r + RS * k < n ? *reinterpret_cast<const f32x4 *>(p) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        p += (int64_t)RS * ld;
     }
 }
 
@@ -381,9 +407,116 @@ __global__ __launch_bounds__(256, 1) void k_mlp_chain_a(WgArgs a) {
     }
 }
 
-// SubDecoderGeoLossl2: x [n, CX] -> W -> W (two square-ish MFMA layers of equal width)
+// SubDecoderGeoLossl with a symbol table.  The chain's first operand is a quantised residual, x = k / scale for an integer k in
+// [lo, hi], and everything before the concatenation depends on k alone: layer 0, layer 1 and the tile part of layer 2's FMA chain
+// (summation order 1 takes the tile channels first).  k_mlp_chain_a_table evaluates that part once per symbol -- row s of the
+// table is the raw layer-2 accumulator of input (lo + s) / scale after the W1 tile channels, through the same wg_layer / wg_mfma
+// sequence as k_mlp_chain_a --, and k_mlp_chain_a_lut starts layer 2 from the row's table entry: 256 instead of 448 MFMAs per
+// wave and tile, 128 instead of 224 weight VGPRs, two LDS tiles, so two workgroups share a CU.  Same bits as k_mlp_chain_a
+// (tests/test_gpu_mlp_chain_lut.py); the table belongs to the weights and is built once.
+template <int W0, int W1, int W2>
+__global__ __launch_bounds__(256, 1) void k_mlp_chain_a_table(WgArgs a, int lo, int n_sym, float scale, float *__restrict__ table) {
+    static_assert(W1 == 128 && W2 == 128 && W0 % 32 == 0, "column blocks of the MFMA layers are split over four waves");
+    __shared__ __attribute__((aligned(16))) float s_p[kTileFloats], s_q[kTileFloats];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 31, lh = lane >> 5;
+    f32x4 B1[W0 / 8], B2[W1 / 8];
+    load_b(B1, a.wp[1], W1 / 32, wv, lane);
+    load_b(B2, a.wp[2], W2 / 32, wv, lane);                    // the tile part: the first W1 / 8 groups of layer 2
+    const int col0 = t % W0;
+    const float w0 = a.w1[col0], b0 = a.bias[0] ? a.bias[0][col0] : 0.0f;
+    const float bia1 = a.bias[1] ? a.bias[1][32 * wv + li] : 0.0f;
+    const float slp0 = (a.act[0] == FPCC_ACT_PRELU && a.slope[0]) ? a.slope[0][0] : 0.0f;
+    const float slp1 = (a.act[1] == FPCC_ACT_PRELU && a.slope[1]) ? a.slope[1][0] : 0.0f;
+    const int row0 = blockIdx.x * kTileRows;
+    with_epilogue(a.act[0], a.clip[0], [&](auto act_c, auto clip_c) {
+#pragma unroll
+        for (int r = t / W0; r < kTileRows; r += 256 / W0) {
+            const int s = row0 + r < n_sym ? row0 + r : n_sym - 1;              // past the last symbol: repeat it, never stored
+            const float x = (float)(lo + s) / scale;                            // k_quantize's expression
+            s_p[r * kPitch + col0] = finish_t<decltype(act_c)::value, decltype(clip_c)::value>(fmaf(x, w0, 0.0f), b0, slp0, a.clip[0]);
+        }
+    });
+    __syncthreads();
+    wg_layer<W0 / 8, 0, 4>(s_p, s_p, s_q, B1, bia1, a.act[1], slp1, a.clip[1], wv, li, lh);
+    __syncthreads();
+    for (int rb = 0; rb < 2; ++rb) {
+        const float *arow = s_q + (32 * rb + li) * kPitch + 4 * lh;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        wg_mfma<W1 / 8>(acc, [&](int g) -> f32x4 { return *reinterpret_cast<const f32x4 *>(arow + 8 * g); }, B2);
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int s = row0 + 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
+            if (s < n_sym) table[s * W2 + 32 * wv + li] = acc[reg];
+        }
+    }
+}
+
+template <int W1, int CY, int W2, int W3>
+__global__ __launch_bounds__(256, 2) void k_mlp_chain_a_lut(WgArgs a, float lo, float hi, float scale, const float *__restrict__ table) {
+    static_assert(W2 == 128 && W3 == 128 && W1 % 32 == 0 && CY % 32 == 0, "column blocks of the MFMA layers are split over four waves");
+    __shared__ __attribute__((aligned(16))) float s_t[2][kTileFloats];
+    __shared__ __attribute__((aligned(16))) int s_idx[kTileRows];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, li = lane & 31, lh = lane >> 5;
+    f32x4 B2[CY / 8], B3[W2 / 8];
+    load_b(B2, a.wp[2] + (W1 / 8) * (W2 / 32) * 256, W2 / 32, wv, lane);          // the concatenated part follows the tile part
+    load_b(B3, a.wp[3], W3 / 32, wv, lane);
+    const float bia2 = a.bias[2] ? a.bias[2][32 * wv + li] : 0.0f, bia3 = a.bias[3] ? a.bias[3][32 * wv + li] : 0.0f;
+    const float slp2 = (a.act[2] == FPCC_ACT_PRELU && a.slope[2]) ? a.slope[2][0] : 0.0f;
+    const float slp3 = (a.act[3] == FPCC_ACT_PRELU && a.slope[3]) ? a.slope[3][0] : 0.0f;
+    // float offset of a row's table entry; the symbol is clamped into the table (NaN -> lo), so no input reads outside it
+    auto entry = [&](float x) -> int { return (int)(fminf(fmaxf(rintf(x * scale), lo), hi) - lo) * W2; };
+    const float *tcol = table + 32 * wv + li;
+
+    f32x4 yv[CY / 16];
+    int ev = 0;
+    unsigned tile = blockIdx.x;
+    if (tile < a.n_tiles) {
+        const int64_t row0 = (int64_t)tile * kTileRows;
+        stage_load_stepped<CY>(yv, a.y, a.ldy, row0, a.n, t);
+        if (t < kTileRows) ev = entry(row0 + t < a.n ? a.x[(row0 + t) * a.ldx] : 0.0f);
+    }
+    // two tiles that swap roles from one 64-row tile to the next: y / output tile and layer-2 tile
+    for (int par = 0; tile < a.n_tiles; tile += gridDim.x, par ^= 1) {
+        const int64_t row0 = (int64_t)tile * kTileRows;
+        float *ty = s_t[par], *tp = s_t[par ^ 1];
+        stage_store<CY>(yv, ty, t);
+        if (t < kTileRows) s_idx[t] = ev;
+        __syncthreads();
+        // layer 2: the accumulators start from the rows' table entries
+        for (int rb = 0; rb < 2; ++rb) {
+            f32x16 acc;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int *ip = s_idx + 32 * rb + 8 * q + 4 * lh;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[4 * q + j] = tcol[ip[j]];
+            }
+            const float *yrow = ty + (32 * rb + li) * kPitch + 4 * lh;
+            wg_mfma<CY / 8>(acc, [&](int g) -> f32x4 { return *reinterpret_cast<const f32x4 *>(yrow + 8 * g); }, B2);
+            wg_store(acc, tp, rb, wv, bia2, a.act[2], slp2, a.clip[2], li, lh);
+        }
+        __syncthreads();
+        // the next tile's inputs travel while layer 3 computes (requested any earlier they do not fit beside layer 2's registers)
+        const unsigned nxt = tile + gridDim.x;
+        if (nxt < a.n_tiles) {
+            const int64_t r1 = (int64_t)nxt * kTileRows;
+            stage_load_stepped<CY>(yv, a.y, a.ldy, r1, a.n, t);
+            if (t < kTileRows) ev = entry(r1 + t < a.n ? a.x[(r1 + t) * a.ldx] : 0.0f);
+        }
+        wg_layer<W2 / 8, 0, 4>(tp, tp, ty, B3, bia3, a.act[3], slp3, a.clip[3], wv, li, lh);
+        __syncthreads();
+        tile_to_global<W3>(ty, a.out, a.ldo, row0, a.n, t);
+        // ty is next written by layer 2 of the following tile, behind that tile's first barrier; tp takes the following tile's y
+        // right away: its last readers (layer 3) are behind the barrier above
+    }
+}
+
+// SubDecoderGeoLossl2: x [n, CX] -> W -> W (two square-ish MFMA layers of equal width).  128 weight VGPRs and two LDS tiles: two
+// workgroups per CU, each wave's barrier waits covered by the other workgroup's waves (profiles/r13/chain_symbol_table.md)
 template <int CX, int W>
-__global__ __launch_bounds__(256, 1) void k_mlp_chain_b(WgArgs a) {
+__global__ __launch_bounds__(256, 2) void k_mlp_chain_b(WgArgs a) {
     static_assert((W == 128 || W == 64) && CX % 32 == 0, "");
     constexpr int NCB = W / 32;
     __shared__ __attribute__((aligned(16))) float s_p[kTileFloats], s_q[kTileFloats];
@@ -534,6 +667,7 @@ extern "C" int fpcc_mlp_chain_f32(const fpcc_mlp_chain *d, void *stream) {
         }
         g.w1 = a.L[0].w1;
         const unsigned grid = g.n_tiles < 256u ? g.n_tiles : 256u;
+        const unsigned grid2 = g.n_tiles < 512u ? g.n_tiles : 512u;          // two workgroups per CU
         const fpcc_mlp_layer *L = d->layers;
         const bool y_ok = d->cat_layer == 2 && d->cy == 128 && aligned16(d->y) && d->ldy % 4 == 0;
         if (d->n_layers == 4 && d->cx == 1 && y_ok && L[0].c_out == 64 && L[1].c_out == 128 && L[2].c_out == 128 && L[3].c_out == 128) {
@@ -541,11 +675,11 @@ extern "C" int fpcc_mlp_chain_f32(const fpcc_mlp_chain *d, void *stream) {
             return check_hip(hipGetLastError(), "k_mlp_chain_a");
         }
         if (d->n_layers == 2 && d->cat_layer < 0 && d->cx == 128 && L[0].c_out == 128 && L[1].c_out == 128) {
-            hipLaunchKernelGGL((k_mlp_chain_b<128, 128>), dim3(grid), dim3(256), 0, as_stream(stream), g);
+            hipLaunchKernelGGL((k_mlp_chain_b<128, 128>), dim3(grid2), dim3(256), 0, as_stream(stream), g);
             return check_hip(hipGetLastError(), "k_mlp_chain_b");
         }
         if (d->n_layers == 2 && d->cat_layer < 0 && d->cx == 64 && L[0].c_out == 64 && L[1].c_out == 64) {
-            hipLaunchKernelGGL((k_mlp_chain_b<64, 64>), dim3(grid), dim3(256), 0, as_stream(stream), g);
+            hipLaunchKernelGGL((k_mlp_chain_b<64, 64>), dim3(grid2), dim3(256), 0, as_stream(stream), g);
             return check_hip(hipGetLastError(), "k_mlp_chain_b");
         }
     }
@@ -555,6 +689,55 @@ extern "C" int fpcc_mlp_chain_f32(const fpcc_mlp_chain *d, void *stream) {
     a.n_waves = waves;
     hipLaunchKernelGGL(k_mlp_chain, dim3((waves + 3) / 4), dim3(256), 0, as_stream(stream), a);
     return check_hip(hipGetLastError(), "k_mlp_chain");
+}
+
+// the descriptor of the one chain shape that has a symbol table (1 -> 64 -> 128 ++ 128 -> 128 -> 128) -> kernel arguments
+static int lut_args(const fpcc_mlp_chain *d, int lo, int hi, float scale, const float *table, bool need_io, WgArgs &g) {
+    if (!d) return fail_arg("mlp_chain_lut: null descriptor");
+    const fpcc_mlp_layer *L = d->layers;
+    if (d->n_layers != 4 || d->cx != 1 || d->cat_layer != 2 || d->cy != 128 || L[0].c_out != 64 || L[1].c_out != 128 ||
+        L[2].c_out != 128 || L[3].c_out != 128)
+        return fail_arg("mlp_chain_lut: the chain 1 -> 64 -> 128 ++ 128 -> 128 -> 128 only");
+    if (hi < lo || (int64_t)hi - lo + 1 > FPCC_MLP_CHAIN_LUT_MAX_SYMBOLS || lo < -(1 << 20) || hi > (1 << 20) || !(scale > 0.0f))
+        return fail_arg("mlp_chain_lut: 1..256 symbols in [-2^20, 2^20] and a positive scale");
+    if (!table || !aligned16(table)) return fail_arg("mlp_chain_lut: null or unaligned table");
+    if (!L[0].w) return fail_arg("mlp_chain_lut: a one-channel first layer needs its plain weights");
+    for (int l = 0; l < 4; ++l) {
+        if (l && (!L[l].w_packed || !aligned16(L[l].w_packed))) return fail_arg("mlp_chain_lut: packed weights required");
+        if (L[l].act != FPCC_ACT_NONE && L[l].act != FPCC_ACT_PRELU && L[l].act != FPCC_ACT_RELU) return fail_arg("mlp_chain_lut: unknown activation");
+        if (L[l].act == FPCC_ACT_PRELU && !L[l].slope) return fail_arg("mlp_chain_lut: PReLU needs a slope pointer");
+        g.wp[l] = l ? L[l].w_packed : nullptr; g.bias[l] = L[l].bias; g.slope[l] = L[l].slope; g.act[l] = L[l].act; g.clip[l] = L[l].clip;
+    }
+    g.w1 = L[0].w;
+    if (need_io) {
+        if (d->n < 0) return fail_arg("mlp_chain_lut: negative row count");
+        if (d->n > 0 && (!d->x || d->ldx < 1 || !d->out || !aligned16(d->out) || d->ldo % 4 || d->ldo < 128))
+            return fail_arg("mlp_chain_lut: null or unaligned input / output");
+        if (d->n > 0 && (!d->y || !aligned16(d->y) || d->ldy % 4 || d->ldy < d->cy)) return fail_arg("mlp_chain_lut: bad concatenation operand");
+        g.x = d->x; g.ldx = d->ldx; g.y = d->y; g.ldy = d->ldy; g.out = d->out; g.ldo = d->ldo; g.n = d->n;
+        g.n_tiles = (unsigned)((d->n + kTileRows - 1) / kTileRows);
+    }
+    return FPCC_OK;
+}
+
+extern "C" int fpcc_mlp_chain_lut_build_f32(const fpcc_mlp_chain *d, int lo, int hi, float scale, float *table, void *stream) {
+    WgArgs g{};
+    if (const int rc = lut_args(d, lo, hi, scale, table, false, g)) return rc;
+    const int n_sym = hi - lo + 1;
+    hipLaunchKernelGGL((k_mlp_chain_a_table<64, 128, 128>), dim3((n_sym + kTileRows - 1) / kTileRows), dim3(256), 0, as_stream(stream), g, lo,
+                       n_sym, scale, table);
+    return check_hip(hipGetLastError(), "k_mlp_chain_a_table");
+}
+
+extern "C" int fpcc_mlp_chain_lut_f32(const fpcc_mlp_chain *d, int lo, int hi, float scale, const float *table, void *stream) {
+    LaunchBracket timed(stream);
+    WgArgs g{};
+    if (const int rc = lut_args(d, lo, hi, scale, table, true, g)) return rc;
+    if (d->n == 0) return FPCC_OK;
+    const unsigned grid = g.n_tiles < 512u ? g.n_tiles : 512u;          // two workgroups per CU
+    hipLaunchKernelGGL((k_mlp_chain_a_lut<128, 128, 128, 128>), dim3(grid), dim3(256), 0, as_stream(stream), g, (float)lo, (float)hi, scale,
+                       table);
+    return check_hip(hipGetLastError(), "k_mlp_chain_a_lut");
 }
 
 extern "C" int fpcc_pointwise_head_f32(const float *x, int c0, int ldx, const float *w1, const float *b1, int c1, int act1,

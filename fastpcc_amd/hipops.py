@@ -7,6 +7,7 @@ there is no alternative implementation: without the library or a GPU these funct
 import collections
 import ctypes as C
 import functools
+import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
@@ -123,6 +124,8 @@ _SIGS = {
     'fpcc_clock_probe': (_i32, [_vp, _i32, _vp]),
     'fpcc_mlp_chain_f32': (_i32, [_vp, _vp]),
     'fpcc_mlp_chain_set_form': (_i32, [_i32]),
+    'fpcc_mlp_chain_lut_build_f32': (_i32, [_vp, _i32, _i32, _f32, _vp, _vp]),
+    'fpcc_mlp_chain_lut_f32': (_i32, [_vp, _i32, _i32, _f32, _vp, _vp]),
     'fpcc_pointwise_head_f32': (_i32, [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _f32, _vp, _i64, _vp]),
     'fpcc_conv_i8_also': (_i32, [_vp, _i32, _i32, _vp, _i32, _i64, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32,
                                  _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp]),
@@ -838,18 +841,34 @@ def mlp_chain_ok(cx: int, widths, cat_layer: int = -1, cy: int = 0) -> bool:
     return 1 <= cat_layer < len(widths) and cy % 32 == 0 and 32 <= cy <= 128
 
 
-def mlp_chain(x: torch.Tensor, layers, y: Optional[torch.Tensor] = None, cat_layer: int = -1,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """A stack of per-point layers as one launch (fpcc_mlp_chain_f32).  layers: sequence of (w [c_in, c_out] contiguous fp32,
-    bias | None, act, slope | None, clip); `y` is concatenated after the activations entering layer `cat_layer`."""
-    px, cx, ldx = _rows2d(x, 'x')
-    n = x.shape[0]
-    d = _MlpChain()
-    d.x, d.cx, d.ldx, d.n, d.n_layers, d.cat_layer = px, cx, ldx, n, len(layers), cat_layer
-    if y is not None:
-        d.y, d.cy, d.ldy = _rows2d(y, 'y')
-        if y.shape[0] != n:
-            raise ValueError('concatenated operand has a different number of rows')
+# The chain 1 -> 64 -> 128 ++ 128 -> 128 -> 128 on a quantised input runs from a symbol table (fpcc_mlp_chain_lut_f32): everything
+# before the concatenation is evaluated once per symbol, not once per row.  FPCC_MLP_CHAIN_LUT=0 keeps fpcc_mlp_chain_f32 for every
+# chain (result-neutral, like FPCC_MLP_CHAIN_WG).  The tables are cached like the packed weight images: one per (weights, symbol
+# range), the entry keeps the tensors it was built from alive and is rebuilt when one of them was written in place.
+MLP_CHAIN_LUT = os.environ.get('FPCC_MLP_CHAIN_LUT', '1') != '0'
+MLP_CHAIN_LUT_MAX_SYMBOLS = 256
+_CHAIN_TABLES: 'collections.OrderedDict' = collections.OrderedDict()
+_CHAIN_TABLES_MAX = 64
+CHAIN_TABLE_BUILDS = 0      # tables built / launches of the table form by this process so far
+CHAIN_LUT_CALLS = 0
+
+
+def mlp_chain_lut_range(cx: int, widths, cat_layer: int, cy: int, sym_range) -> Optional[Tuple[int, int, float]]:
+    """(lo, hi, scale) when a chain of this shape whose input holds k / scale for integers lo <= k <= hi (`sym_range` = (lo, hi,
+    scale) or None: not known) runs from a symbol table, None when it runs as the general chain"""
+    if not MLP_CHAIN_LUT or sym_range is None:
+        return None
+    lo, hi, scale = sym_range
+    if (cx, tuple(widths), cat_layer, cy) != (1, (64, 128, 128, 128), 2, 128):
+        return None
+    lo, hi, scale = int(lo), int(hi), float(scale)
+    if hi < lo or hi - lo + 1 > MLP_CHAIN_LUT_MAX_SYMBOLS or min(lo, -hi) < -(1 << 20) or not scale > 0.0:
+        return None
+    return lo, hi, scale
+
+
+def _chain_layers(d, layers, cx: int, cat_layer: int):
+    """fills the layers of the chain descriptor `d` (cy set) -> (the packed images to keep alive, width of the last layer, flop per row)"""
     keep = []
     c_in = cx
     flops = 0
@@ -870,14 +889,85 @@ def mlp_chain(x: torch.Tensor, layers, y: Optional[torch.Tensor] = None, cat_lay
         L.bias = _dev(bias, torch.float32, 'bias', True)
         L.slope = _dev(slope, torch.float32, 'slope', True)
         L.c_out, L.act, L.clip = c_out, int(act), float(clip)
-        flops += 2 * n * c_in * c_out
+        flops += 2 * c_in * c_out
         c_in = c_out
+    return keep, c_in, flops
+
+
+def mlp_chain_lut_table(layers, lo: int, hi: int, scale: float) -> torch.Tensor:
+    """the symbol table [hi - lo + 1, 128] of the chain 1 -> 64 -> 128 ++ 128 -> 128 -> 128 with these `layers` (as for mlp_chain): row s =
+    the raw accumulator of layer 2 after the 128 channels of layer 1, for the input (lo + s) / scale.  Cached; do not write to it."""
+    if mlp_chain_lut_range(1, [w.shape[1] for w, *_ in layers], 2, 128, (lo, hi, scale)) is None:
+        raise ValueError('no symbol table for this chain and symbol range')
+    d = _MlpChain()
+    d.cx, d.cy, d.cat_layer, d.n_layers = 1, 128, 2, len(layers)
+    keep = _chain_layers(d, layers, 1, 2)
+    table = _chain_table(d, layers, int(lo), int(hi), float(scale))
+    del keep
+    return table
+
+
+def _chain_table(d, layers, lo: int, hi: int, scale: float) -> torch.Tensor:
+    """the table of fpcc_mlp_chain_lut_build_f32 for the chain descriptor `d` (its layers filled in), cached"""
+    global CHAIN_TABLE_BUILDS
+    # what the table is computed from: layers 0 and 1 whole, the weights of layer 2
+    src = [t for w, bias, _, slope, _ in layers[:2] for t in (w, bias, slope)] + [layers[2][0]]
+    key = (tuple(None if t is None else (t.data_ptr(), t.numel()) for t in src),
+           tuple((int(a), float(c)) for _, _, a, _, c in layers[:2]), lo, hi, scale)
+    versions = tuple(None if t is None else t._version for t in src)
+    ent = _CHAIN_TABLES.get(key)
+    if ent is not None and ent[1] == versions:
+        _CHAIN_TABLES.move_to_end(key)
+        return ent[2]
+    table = torch.empty((hi - lo + 1, 128), dtype=torch.float32, device=src[0].device)
+    _ok(lib().fpcc_mlp_chain_lut_build_f32(C.byref(d), lo, hi, scale, table.data_ptr(), _stream()))
+    CHAIN_TABLE_BUILDS += 1
+    _CHAIN_TABLES[key] = (src, versions, table)
+    while len(_CHAIN_TABLES) > _CHAIN_TABLES_MAX:
+        _CHAIN_TABLES.popitem(last=False)
+    return table
+
+
+def mlp_chain(x: torch.Tensor, layers, y: Optional[torch.Tensor] = None, cat_layer: int = -1,
+              out: Optional[torch.Tensor] = None, sym_range=None) -> torch.Tensor:
+    """A stack of per-point layers as one launch (fpcc_mlp_chain_f32).  layers: sequence of (w [c_in, c_out] contiguous fp32,
+    bias | None, act, slope | None, clip); `y` is concatenated after the activations entering layer `cat_layer`.
+    sym_range = (lo, hi, scale): the caller's promise that x holds k / scale for integers lo <= k <= hi (a quantised residual); where
+    mlp_chain_lut_range takes it the chain runs from a symbol table (fpcc_mlp_chain_lut_f32), same bits."""
+    global CHAIN_LUT_CALLS
+    px, cx, ldx = _rows2d(x, 'x')
+    n = x.shape[0]
+    d = _MlpChain()
+    d.x, d.cx, d.ldx, d.n, d.n_layers, d.cat_layer = px, cx, ldx, n, len(layers), cat_layer
+    if y is not None:
+        d.y, d.cy, d.ldy = _rows2d(y, 'y')
+        if y.shape[0] != n:
+            raise ValueError('concatenated operand has a different number of rows')
+    keep, c_in, flops = _chain_layers(d, layers, cx, cat_layer)
+    flops *= n
     if out is None:
         out = torch.empty((n, c_in), dtype=torch.float32, device=x.device)
     d.out, co, d.ldo = _rows2d(out, 'out')
     if co != c_in or out.shape[0] != n:
         raise ValueError('output shape mismatch')
     fn, ref, stream = lib().fpcc_mlp_chain_f32, C.byref(d), _stream()
+    lut = mlp_chain_lut_range(cx, [w.shape[1] for w, *_ in layers], cat_layer, d.cy, sym_range)
+    if lut is not None:
+        CHAIN_LUT_CALLS += 1
+        table = _chain_table(d, layers, *lut)
+        fn, call = lib().fpcc_mlp_chain_lut_f32, (ref, lut[0], lut[1], lut[2], table.data_ptr(), stream)
+        trace = _current_trace()
+        if trace is None:
+            _untraced_launch(fn, call)
+            return out
+        # the work that is needed: layer 2 over the concatenated operand and layer 3
+        w2, w3 = layers[2][0], layers[3][0]
+        _traced_launch(trace, fn, call, {'mfma': True, 'chain': True, 'lut': True, 'c_in': cx, 'c_out': c_in, 'n_out': n, 'groups': 1,
+                                         'n_offsets': 1, 'nbr': None, 'nbr_ks': 0, 'nbr_os': 1,
+                                         'flops': 2.0 * n * (d.cy * w2.shape[1] + w3.shape[0] * w3.shape[1]),
+                                         'bytes': 4.0 * n * (cx + d.cy + c_in) + 4.0 * (d.cy * w2.shape[1] + w3.numel() + table.numel()),
+                                         'layers': [tuple(w.shape) for w, *_ in layers]})
+        return out
     trace = _current_trace()
     if trace is None:
         _untraced_launch(fn, (ref, stream))

@@ -68,11 +68,12 @@ FUSE_MLP_CHAINS = True
 CHAIN_CALLS = 0
 
 
-def mlp_chain_forward(blocks, x, y=None, cat_layer: int = -1, clip: float = 0.0):
+def mlp_chain_forward(blocks, x, y=None, cat_layer: int = -1, clip: float = 0.0, sym_range=None):
     """`blocks`: MEMLPBlocks applied in sequence to x (SparseTensor or [n, C] tensor); `y` (SparseTensor) is concatenated
     after the activations entering block `cat_layer` (ME.cat(h, y)).  Returns the features [n, C_out] of the last block, or
     None when the stack cannot run fused (training / autograd, batch norm, an activation that does not fuse, shapes outside
-    fpcc_mlp_chain_f32): the caller then evaluates block by block."""
+    fpcc_mlp_chain_f32): the caller then evaluates block by block.  `sym_range` = (lo, hi, scale) when x is known to hold k / scale
+    for integer symbols lo <= k <= hi (hipops.mlp_chain: such a chain may run from a symbol table, same bits)."""
     global CHAIN_CALLS
     from . import hipops as ops
     if not FUSE_MLP_CHAINS or torch.is_grad_enabled():
@@ -97,7 +98,7 @@ def mlp_chain_forward(blocks, x, y=None, cat_layer: int = -1, clip: float = 0.0)
         layers.append((b.mlp._weight_t(), None if bias is None else bias.detach(), act.kind, act.slope,
                        clip if i == len(blocks) - 1 else 0.0))
     CHAIN_CALLS += 1
-    return ops.mlp_chain(xf, layers, y=yf, cat_layer=cat_layer)
+    return ops.mlp_chain(xf, layers, y=yf, cat_layer=cat_layer, sym_range=sym_range)
 
 
 class BaseConvBlock(nn.Module):

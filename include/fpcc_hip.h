@@ -355,6 +355,18 @@ int fpcc_mlp_chain_f32(const fpcc_mlp_chain *chain, void *stream);
  * workgroup form that keeps the weights in registers (default), 0 = every chain in the wave form; negative = query.  Returns
  * the previous setting. */
 int fpcc_mlp_chain_set_form(int form);
+/* The chain 1 -> 64 -> 128, cat(., y[128]) -> 128 -> 128 (SubDecoderGeoLossl) on a QUANTISED one-channel input: x = k / scale for an
+ * integer symbol k in [lo, hi] (what fpcc_quantize_symbols leaves in place; the decoder's int32 symbol / scale).  Layer 0, layer 1
+ * and the first 128 terms of layer 2's FMA chain (summation order 1: the previous layer's channels come first) depend on k alone.
+ * fpcc_mlp_chain_lut_build_f32 evaluates them once per symbol into `table` [hi - lo + 1][128] fp32 (row s = the raw layer-2
+ * accumulator of input (lo + s) / scale); fpcc_mlp_chain_lut_f32 then runs the chain from the rows' table entries, row index
+ * rint(x * scale) - lo CLAMPED into the table.  For inputs inside [lo, hi] / scale the output has the bits of fpcc_mlp_chain_f32;
+ * 57 % of its matrix work.  The table depends on the weights, biases, activations of layers 0..2 and on (lo, hi, scale): build it
+ * again when any of them changes.  1 <= hi - lo + 1 <= FPCC_MLP_CHAIN_LUT_MAX_SYMBOLS; other shapes are refused.  `chain` of the
+ * build call needs its layers only (x, y, out, n are ignored). */
+#define FPCC_MLP_CHAIN_LUT_MAX_SYMBOLS 256
+int fpcc_mlp_chain_lut_build_f32(const fpcc_mlp_chain *chain, int lo, int hi, float scale, float *table, void *stream);
+int fpcc_mlp_chain_lut_f32(const fpcc_mlp_chain *chain, int lo, int hi, float scale, const float *table, void *stream);
 /* Narrow per-point head C0 -> C1 -> 1 (the decoder's classify block, models/convolutional/lossy_coord_v2/layers.py:105-110:
  * ConvBlock(16, 8, 1, 1) + ConvBlock(8, 1, 1, 1) on the 8 N candidates) as one launch, one thread per row:
  *     out[o] = act2(sum_j act1(sum_c x[o][c] w1[c][j] + b1[j]) w2[j] + b2), clamped to [-clip, clip] when clip > 0.
