@@ -39,6 +39,9 @@
 // (256 B).  On the bench's 286 K .. 4.36 M-row maps the 64-row unit executes 2.2-2.6 % more pairs and the 27-offset launches take
 // about 3 % less time in all (per shape 2-6 % less; single launches between 6 % less and 2 % more): profiles/r07/fold64.md.
 #include "conv_common.h"
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 
@@ -2099,6 +2102,133 @@ extern "C" int fpcc_conv_row_keys(const int32_t *nbr, int n_offsets, int64_t nbr
     hipLaunchKernelGGL(k_conv_row_keys, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), nbr, n_offsets, nbr_ks,
                        nbr_os, n, window_log2, keys_out, masks_out);
     return check_hip(hipGetLastError(), "k_conv_row_keys");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Row order in whole units (fpcc_conv_row_order_units).  The windowed order above ends every (window, pattern) run whose length is no
+// multiple of the unit height in a unit of two patterns, which executes the union of both for all its rows: on a batch-sized map a
+// quarter of the rows sit in such units and the 64-row units execute 1.057x the (row, offset) pairs the rows have.  Here the whole
+// units of every run stay where they are and the tails of ALL windows are pooled and sorted by pattern: the executed pairs of a
+// whole-map sort (1.012x at 4.36 M rows) with three quarters of the rows still window-local.
+namespace fpcc {
+namespace {
+__device__ __forceinline__ uint32_t gray_rank(uint32_t m) {
+    m ^= m >> 1; m ^= m >> 2; m ^= m >> 4; m ^= m >> 8; m ^= m >> 16;
+    return m;
+}
+
+// The two sorts of the specification (by (window, rank), then by whole ? 0 : 1 + rank) are done in the other order, which gives the
+// same permutation with fewer sort passes.  A stable sort by RANK alone leaves the rows (rank, position)-ordered: the runs of equal
+// (rank, window) are contiguous in it as well, with the same rows in the same (position) order, so "whole" is the same predicate;
+// and the tails are then already in their final order -- by rank, inside a rank by window and position.  A second stable sort by
+// key2 = whole ? window : n_windows moves the whole rows in front, by window and inside a window by (rank, position) as before,
+// and keeps the tails as they are.  n_off bits + (window bits + 1) bits instead of (n_off + window bits) + (n_off + 1): five 8-bit
+// passes instead of eight at 4.36 M rows and 27 offsets, all on 32-bit keys.
+
+// the rows' Gray ranks, and the identity permutation the sort carries along
+__global__ void k_row_units_ranks(const uint32_t *__restrict__ masks, const int32_t *__restrict__ nbr, int n_off, int64_t nbr_ks,
+                                  int64_t nbr_os, int64_t n, uint32_t *__restrict__ rank, int32_t *__restrict__ iota,
+                                  uint32_t *__restrict__ masks_out) {
+    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= n) return;
+    uint32_t m = 0;
+    if (masks) {
+        m = masks[o] & (0xffffffffu >> (32 - n_off));
+    } else {
+        for (int k = 0; k < n_off; ++k) m |= (nbr[(int64_t)k * nbr_ks + o * nbr_os] >= 0 ? 1u : 0u) << k;
+        if (masks_out) masks_out[o] = m;
+    }
+    rank[o] = gray_rank(m);
+    iota[o] = (int32_t)o;
+}
+
+// rank[i], row[i]: the rows sorted by rank (stable).  head[i] = i where a run of equal (rank, window) starts, 0 elsewhere: its
+// inclusive maximum scan is every element's run start
+__global__ void k_row_units_heads(const uint32_t *__restrict__ rank, const int32_t *__restrict__ row, int64_t n, int window_log2,
+                                  int32_t *__restrict__ head) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    head[i] = (i > 0 && (rank[i] != rank[i - 1] || (row[i] >> window_log2) != (row[i - 1] >> window_log2))) ? (int32_t)i : 0;
+}
+
+// the last element of every run writes the run's length at the run's start
+__global__ void k_row_units_lengths(const uint32_t *__restrict__ rank, const int32_t *__restrict__ row, const int32_t *__restrict__ start,
+                                    int64_t n, int window_log2, int32_t *__restrict__ len) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (i == n - 1 || rank[i] != rank[i + 1] || (row[i] >> window_log2) != (row[i + 1] >> window_log2))
+        len[start[i]] = (int32_t)(i - start[i] + 1);
+}
+
+// key2 = the window for the rows of a run's whole units, n_windows for its tail
+__global__ void k_row_units_key2(const int32_t *__restrict__ row, const int32_t *__restrict__ start, const int32_t *__restrict__ len,
+                                 int64_t n, int window_log2, int unit, uint32_t n_windows, uint32_t *__restrict__ key2) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t s = start[i];
+    const int32_t whole = len[s] / unit * unit;
+    key2[i] = (int32_t)i - s < whole ? (uint32_t)(row[i] >> window_log2) : n_windows;
+}
+}  // namespace
+}  // namespace fpcc
+
+extern "C" int64_t fpcc_conv_row_order_units(const uint32_t *masks, const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                                             int64_t n, int window_log2, int unit, int32_t *order_out, uint32_t *masks_out, void *ws,
+                                             int64_t ws_bytes, void *stream) {
+    if (n < 0 || n > INT32_MAX || n_offsets < 1 || n_offsets > 31 || window_log2 < 5 || window_log2 > 30 || (unit != 32 && unit != 64))
+        return fail_arg("conv_row_order_units: sizes out of range");
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    const bool one_window = n <= ((int64_t)1 << window_log2);
+    const uint32_t n_windows = (uint32_t)(((int64_t)nn - 1) >> window_log2) + 1;
+    unsigned bits2 = 1;                                          // key2 takes the values 0 .. n_windows
+    while (bits2 < 32 && (n_windows >> bits2)) ++bits2;
+    size_t sort1 = 0, sort2 = 0, scan = 0;
+    FPCC_HIP(rocprim::radix_sort_pairs(nullptr, sort1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
+                                       (int32_t *)nullptr, nn, 0u, (unsigned)n_offsets));
+    FPCC_HIP(rocprim::radix_sort_pairs(nullptr, sort2, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
+                                       (int32_t *)nullptr, nn, 0u, bits2));
+    FPCC_HIP(rocprim::inclusive_scan(nullptr, scan, (const int32_t *)nullptr, (int32_t *)nullptr, nn, rocprim::maximum<int32_t>()));
+    // workspace: 5 x 32-bit [n] | scratch of the sorts and the scan
+    const int64_t arr = align_up((int64_t)(4 * nn), 256);
+    const int64_t tmp_bytes = align_up((int64_t)std::max(std::max(sort1, sort2), scan), 256);
+    const int64_t need = 5 * arr + tmp_bytes;
+    if (!ws) return need;
+    if (ws_bytes < need) {
+        set_error("conv_row_order_units: workspace %lld < %lld", (long long)ws_bytes, (long long)need);
+        return FPCC_E_WORKSPACE;
+    }
+    if (n == 0) return FPCC_OK;
+    if ((!masks && !nbr) || !order_out) return fail_arg("conv_row_order_units: null pointer");
+    char *p = static_cast<char *>(ws);
+    uint32_t *rank_in = reinterpret_cast<uint32_t *>(p), *rank = reinterpret_cast<uint32_t *>(p + arr);
+    int32_t *iota = reinterpret_cast<int32_t *>(p + 2 * arr), *row = reinterpret_cast<int32_t *>(p + 3 * arr);
+    uint32_t *key2 = reinterpret_cast<uint32_t *>(p + 4 * arr);
+    void *tmp = p + 5 * arr;
+    hipStream_t s = fpcc::as_stream(stream);
+    const dim3 grid(blocks_for(n, 256)), block(256);
+
+    hipLaunchKernelGGL(k_row_units_ranks, grid, block, 0, s, masks, nbr, n_offsets, nbr_ks, nbr_os, n, rank_in, iota, masks_out);
+    FPCC_LAUNCHED(k_row_units_ranks);
+    if (one_window) row = order_out;                             // one window: the rows by rank are the order
+    FPCC_HIP(rocprim::radix_sort_pairs(tmp, sort1, (const uint32_t *)rank_in, rank, (const int32_t *)iota, row, (size_t)n, 0u,
+                                       (unsigned)n_offsets, s));
+    if (one_window) return FPCC_OK;
+
+    // the unsorted ranks and the identity are spent: their space holds the run lengths, the run starts and then the sorted key2
+    int32_t *len = reinterpret_cast<int32_t *>(rank_in), *start = iota, *head = reinterpret_cast<int32_t *>(key2);
+    hipLaunchKernelGGL(k_row_units_heads, grid, block, 0, s, (const uint32_t *)rank, (const int32_t *)row, n, window_log2, head);
+    FPCC_LAUNCHED(k_row_units_heads);
+    FPCC_HIP(rocprim::inclusive_scan(tmp, scan, (const int32_t *)head, start, (size_t)n, rocprim::maximum<int32_t>(), s));
+    hipLaunchKernelGGL(k_row_units_lengths, grid, block, 0, s, (const uint32_t *)rank, (const int32_t *)row, (const int32_t *)start, n,
+                       window_log2, len);
+    FPCC_LAUNCHED(k_row_units_lengths);
+    hipLaunchKernelGGL(k_row_units_key2, grid, block, 0, s, (const int32_t *)row, (const int32_t *)start, (const int32_t *)len, n,
+                       window_log2, unit, n_windows, key2);
+    FPCC_LAUNCHED(k_row_units_key2);
+    uint32_t *key2_sorted = reinterpret_cast<uint32_t *>(start);
+    FPCC_HIP(rocprim::radix_sort_pairs(tmp, sort2, (const uint32_t *)key2, key2_sorted, (const int32_t *)row, order_out, (size_t)n, 0u,
+                                       bits2, s));
+    return FPCC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -410,6 +410,10 @@ class CoordinateManager:
     ROW_ORDER_WINDOW_LOG2 = int(os.environ.get('FPCC_ROW_WINDOW_LOG2', '19'))
 
     ROW_ORDER_MIN_ROWS_TRAINING = 512         # the weight gradient skips absent (row block, offset) pairs on any map
+    # inference maps that run the 64-row folded unit (kFold64Rows of conv.hip) take their row order in whole 64-row units
+    # (fpcc_conv_row_order_units); FPCC_ROW_ORDER_UNITS=0 gives them the plain windowed order of every other map
+    ROW_ORDER_UNIT_ROWS = 200 * 1024
+    ROW_ORDER_UNITS = os.environ.get('FPCC_ROW_ORDER_UNITS', '1') != '0'
 
     def _row_order(self, m: _Map, training: bool = False) -> Optional[torch.Tensor]:
         """permutation of m's rows that groups like neighbour patterns into the same 32-row MFMA block; cached per map and
@@ -420,8 +424,9 @@ class CoordinateManager:
                 nbr = self._nbr27(m, want_rows=not training)
                 # the masks of a table made by nbr27_from_parent_ex describe exactly that table (a mask derived earlier from the parent
                 # level does too: same rule); without them the keys are read off the table
+                unit = 64 if self.ROW_ORDER_UNITS and not training and m.n >= self.ROW_ORDER_UNIT_ROWS else None
                 m.row_order = ops.conv_row_order(nbr, 27, m.n, 1, m.n, self.ROW_ORDER_WINDOW_LOG2,
-                                                 masks=m.mask27 if m.nbr27_rows is not None else None)
+                                                 masks=m.mask27 if m.nbr27_rows is not None else None, unit=unit)
         return m.row_order
 
     def _k2_order(self, src: _Map):

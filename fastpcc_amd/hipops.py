@@ -35,6 +35,7 @@ _SIGS = {
     'fpcc_nbr27_from_parent': (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'fpcc_nbr27_from_parent_ex': (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     'fpcc_conv_row_keys_masks': (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    'fpcc_conv_row_order_units': (_i64, [_vp, _vp, _i32, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_gather_table_rows_i32': (_i32, [_vp, _i32, _vp, _i64, _vp, _vp]),
     'fpcc_mask27_from_parent': (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     'fpcc_conv_ones_k3_f32': (_i32, [_vp, _i64, _vp, _vp, _i32, _i32, _vp, C.c_float, _vp, _i32, _vp]),
@@ -1277,24 +1278,36 @@ def noisy_normal_bits(y: torch.Tensor, index: torch.Tensor, log_scale_offset: fl
 
 
 def conv_row_order(nbr: Optional[torch.Tensor], n_offsets: int, nbr_ks: int, nbr_os: int, n: int, window_log2: int = 13,
-                   heaviest_first: bool = True, masks: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   heaviest_first: bool = True, masks: Optional[torch.Tensor] = None, unit: Optional[int] = None) -> torch.Tensor:
     """permutation of the n output rows that puts rows with like neighbour patterns into the same MFMA block (windows of
     2^window_log2 rows) and, tile by tile, the tiles that execute most kernel offsets first; pass it to
-    conv_f32(row_order=...) / conv_i8(row_order=...)"""
+    conv_f32(row_order=...) / conv_i8(row_order=...).  unit = 32 or 64: the order in whole units of that many rows
+    (fpcc_conv_row_order_units: every window keeps its single-pattern units, the tails of all windows are pooled by pattern)"""
     L = lib()
     dev = masks.device if masks is not None else nbr.device
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    group = 64 if n >= 32 * 1024 else 32              # the tile heights fpcc_conv_f32 uses for these map sizes
+    group = unit or (64 if n >= 32 * 1024 else 32)    # the tile heights fpcc_conv_f32 uses for these map sizes
     n_groups = n // group
     # (on maps of millions of rows the launch has no tail worth shaping and the extra sort costs more than it returns)
     heaviest_first = heaviest_first and 2 <= n_groups <= LPT_MAX_GROUPS
-    if masks is not None:                             # the rows' presence masks exist (the table's producer wrote them): 4 bytes per row
-        _ok(L.fpcc_conv_row_keys_masks(_dev(masks, torch.int32, 'masks'), n, window_log2, keys.data_ptr(), _stream()))
+    if unit is not None:
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        have = masks is not None
+        if not have:
+            masks = torch.empty(n, dtype=torch.int32, device=dev) if heaviest_first else None
+        args = ((_dev(masks, torch.int32, 'masks'), None) if have else (None, _dev(nbr, torch.int32, 'nbr'))) + \
+               (n_offsets, nbr_ks, nbr_os, n, window_log2, unit)
+        ws, need = _ws(lambda: L.fpcc_conv_row_order_units(*args, None, None, None, 0, None), dev)
+        _ok(L.fpcc_conv_row_order_units(*args, order.data_ptr(), None if have or masks is None else masks.data_ptr(), ws.data_ptr(),
+                                        need, _stream()))
     else:
-        masks = torch.empty(n, dtype=torch.int32, device=dev) if heaviest_first else None
-        _ok(L.fpcc_conv_row_keys(_dev(nbr, torch.int32, 'nbr'), n_offsets, nbr_ks, nbr_os, n, window_log2, keys.data_ptr(),
-                                 None if masks is None else masks.data_ptr(), _stream()))
-    order = sort_keys(keys, 32 + max(1, (n >> window_log2).bit_length()))[1]
+        keys = torch.empty(n, dtype=torch.int64, device=dev)
+        if masks is not None:                         # the rows' presence masks exist (the table's producer wrote them): 4 bytes per row
+            _ok(L.fpcc_conv_row_keys_masks(_dev(masks, torch.int32, 'masks'), n, window_log2, keys.data_ptr(), _stream()))
+        else:
+            masks = torch.empty(n, dtype=torch.int32, device=dev) if heaviest_first else None
+            _ok(L.fpcc_conv_row_keys(_dev(nbr, torch.int32, 'nbr'), n_offsets, nbr_ks, nbr_os, n, window_log2, keys.data_ptr(),
+                                     None if masks is None else masks.data_ptr(), _stream()))
+        order = sort_keys(keys, 32 + max(1, (n >> window_log2).bit_length()))[1]
     if not heaviest_first:
         return order
     gkeys = torch.empty(n_groups, dtype=torch.int64, device=dev)

@@ -408,6 +408,21 @@ int fpcc_conv_tile_keys(const uint32_t *row_masks, int n_offsets, const int32_t 
 int fpcc_conv_group_order(const int64_t *group_keys, int64_t n_groups, int32_t *perm_out, void *stream);
 int fpcc_conv_regroup_rows(const int32_t *row_order, const int32_t *group_perm, int64_t n, int group, int32_t *row_order_out,
                            void *stream);
+/* Row order in whole units.  The windowed pattern order above ends every (window, pattern) run whose length is no multiple of
+ * the unit height in a unit that mixes two patterns -- a quarter of the rows of a batch-sized map sit in such units.  This builder
+ * keeps whole units per window and pools the tails over the whole map, in one call and without leaving the device:
+ *   1. stable sort of the rows by key1 = (row >> window_log2, Gray rank of the row's mask)  -- the order of fpcc_conv_row_keys;
+ *   2. in that sequence a row is WHOLE if its index inside its run of equal key1 is below (run length / unit) * unit;
+ *   3. stable sort of that sequence by key2 = whole ? 0 : 1 + Gray rank: the whole rows first, in their order (a multiple of
+ *      `unit` rows, every unit one pattern), then the tails of all windows in pattern order;
+ *   with n <= 2^window_log2 (one window) the order of step 1 is returned.
+ * masks (n presence masks, bits >= n_offsets ignored) or, with masks == NULL, the table `nbr` laid out as for fpcc_conv_row_keys;
+ * masks_out (may be NULL) receives the masks read off the table.  n_offsets in [1, 31], window_log2 in [5, 30], unit 32 or 64,
+ * n < 2^31.  Returns the workspace size in bytes when ws == NULL, else FPCC_OK or a negative error; allocates nothing, reads
+ * nothing back and does not synchronise. */
+int64_t fpcc_conv_row_order_units(const uint32_t *masks, const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                                  int64_t n, int window_log2, int unit, int32_t *order_out, uint32_t *masks_out, void *ws,
+                                  int64_t ws_bytes, void *stream);
 /* THE classification of a convolution shape (numerics version 3): where fpcc_conv_f32 / fpcc_conv_f32_pk evaluate it, in which
  * summation order, which packed weight image it reads.  A function of (c1, c2, c_out, n_offsets, groups) and of knob 7 (experiments
  * only) -- never of a row count, of the caller's operands or of another knob -- so a caller may cache it per shape.  The one question
