@@ -21,6 +21,8 @@ Sources of truth used:
   hilbert.json   keys of the reference's Hilbert state machine (table read from hilbert3d.cu, loop evaluated on the host)
   codec_v2.json  the reference's lossy_coord_v2 codec (layers / model / geo_lossl_em / ME wrapper layers + its rANS coders) executed on
                  the CPU over a functional MinkowskiEngine stand-in built on oracle/coords.py + conv_mm: streams, reconstructions
+  codec_v2_rates_chain.json  the same model code in chain mode (as codec_v2_chain.json) at the real widths of baseline_r3 / baseline_r5 /
+                 expanded_r3 / expanded_r5, each YAML read by the reference's own loader
   get_keep.json  the reference's Decoder.get_keep (lossy_coord_v2/layers.py:151-180) executed over the same stand-in on seeded
                  candidate sets: logits, requested point counts, the keep masks it returned
   codec_color.json / codec_lossl.json  likewise the reference's lossy_coord_lossy_color codec (over the MinkowskiEngine stand-in) and its
@@ -1637,12 +1639,71 @@ def make_codec_v2_chain():
     and linear layer summed in the order the HIP kernels document (oracle/orders.py, the restatement of the numerics version of
     include/fpcc_hip.h).  These streams are what the GPU path has to write byte for byte, and their reconstructions point for point --
     the mm-mode runs of codec_v2.json sum in torch's CPU order and can only be matched within tolerances."""
-    import torch
     PCC, ModelConfig, hipops = _chain_env_v2()
-    from fastpcc_amd.synthetic import batched, enliven, surface_cloud
+    from fastpcc_amd.synthetic import surface_cloud
     out = {'numerics_version': hipops.numerics_version(), 'runs': []}
     base = dict(activation='prelu', compressed_channels=(1,), skip_encoding_fea=1, adaptive_pruning=True)
+    run = _chain_run_v2(PCC, out, 'codec_v2_chain')
 
+    for label, kw, seed, res, pts in (
+            ('r1_like', dict(encoder_channels=(8, 16), decoder_channels=(8,), geo_lossl_if_sample=(0, 1, 0, 1, 0, 1),
+                             geo_lossl_channels=(16, 32, 32, 32, 32, 32, 1)), 1, 64, 2500),
+            ('r3_like_two_stages', dict(encoder_channels=(8, 16, 16), decoder_channels=(16, 8), geo_lossl_if_sample=(0, 1, 0, 1),
+                                        geo_lossl_channels=(16, 32, 32, 32, 1)), 2, 64, 3000)):
+        cfg = ModelConfig()
+        for k, v in {**base, **kw}.items():
+            assert hasattr(cfg, k), k
+            setattr(cfg, k, v)
+        cfg.check()
+        run(label, cfg, {k: (list(v) if isinstance(v, tuple) else v) for k, v in {**base, **kw}.items()}, seed,
+            surface_cloud(seed + 40, res, pts) + np.array([2, 0, 5], dtype=np.int32))
+    # the headline configuration at its real widths, from the reference's own YAML through its own config loader
+    from lib.config import Config as RefConfig
+    ref_cfg = RefConfig()
+    ref_cfg.merge_with_yaml(os.path.join(REF, 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'))
+    ref_cfg.check()
+    mc = ref_cfg.model
+    run('baseline_r1_yaml', mc, {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in vars(mc).items() if not k.startswith('_')}, 6,
+        surface_cloud(46, 256, 4000) + np.array([1, 4, 2], dtype=np.int32), {'yaml': 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'})
+    run('baseline_r1_yaml_12k', mc, {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in vars(mc).items() if not k.startswith('_')}, 7,
+        surface_cloud(47, 256, 16000) + np.array([3, 1, 0], dtype=np.int32), {'yaml': 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'})
+    return out
+
+
+def make_codec_v2_rates_chain():
+    """The higher object rate points at their REAL widths, as make_codec_v2_chain does for baseline_r1.yaml: baseline_r3 / baseline_r5
+    (two and three generative decoder stages) and expanded_r3 / expanded_r5 (256-wide lossless pyramid below the finest level), each
+    read by the reference's own config loader from its own YAML and run by the reference's own model code in chain mode, all on one
+    128^3 surface cloud."""
+    PCC, ModelConfig, hipops = _chain_env_v2()
+    from fastpcc_amd.synthetic import surface_cloud
+    from lib.config import Config as RefConfig
+    out = {'numerics_version': hipops.numerics_version(), 'runs': []}
+    run = _chain_run_v2(PCC, out, 'codec_v2_rates_chain')
+    # 256^3, not 128^3: all four pyramids reach tensor stride 128, and the reference's coder asserts on a cloud whose bottom level is a
+    # single voxel (see make_codec_v2_partitions_chain)
+    xyz = surface_cloud(48, 256, 5000) + np.array([2, 5, 1], dtype=np.int32)
+    for seed, name in ((11, 'baseline_r3'), (12, 'baseline_r5'), (13, 'expanded_r3'), (14, 'expanded_r5')):
+        path = f'config/convolutional/lossy_coord_v2/{name}.yaml'
+        ref_cfg = RefConfig()
+        cwd = os.getcwd()
+        os.chdir(REF)                    # these files name their `# include` from the reference's root, its working directory
+        try:
+            ref_cfg.merge_with_yaml(path)
+        finally:
+            os.chdir(cwd)
+        ref_cfg.check()
+        mc = ref_cfg.model
+        run(name + '_yaml', mc, {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in vars(mc).items() if not k.startswith('_')},
+            seed, xyz, {'yaml': path})
+    return out
+
+
+def _chain_run_v2(PCC, out, tag):
+    """-> run(label, cfg, cfg_dict, seed, xyz, extra=None): one chain-mode run of the reference's PCC (seeded weights, shuffled input
+    rows) whose entry is appended to out['runs']; shared by make_codec_v2_chain and make_codec_v2_rates_chain"""
+    import torch
+    from fastpcc_amd.synthetic import batched, enliven
     from oracle import sparse_conv as sc_
     real_sigmoid = torch.Tensor.sigmoid
 
@@ -1669,31 +1730,9 @@ def make_codec_v2_chain():
                  'stream_hex': data.hex(), 'recon_points': len(rec), 'recon_sha256': hashlib.sha256(keys.tobytes()).hexdigest()}
         entry.update(extra or {})
         out['runs'].append(entry)
-        print('codec_v2_chain', label, len(xyz), 'points ->', len(data), 'bytes,', len(rec), 'decoded')
+        print(tag, label, len(xyz), 'points ->', len(data), 'bytes,', len(rec), 'decoded')
 
-    for label, kw, seed, res, pts in (
-            ('r1_like', dict(encoder_channels=(8, 16), decoder_channels=(8,), geo_lossl_if_sample=(0, 1, 0, 1, 0, 1),
-                             geo_lossl_channels=(16, 32, 32, 32, 32, 32, 1)), 1, 64, 2500),
-            ('r3_like_two_stages', dict(encoder_channels=(8, 16, 16), decoder_channels=(16, 8), geo_lossl_if_sample=(0, 1, 0, 1),
-                                        geo_lossl_channels=(16, 32, 32, 32, 1)), 2, 64, 3000)):
-        cfg = ModelConfig()
-        for k, v in {**base, **kw}.items():
-            assert hasattr(cfg, k), k
-            setattr(cfg, k, v)
-        cfg.check()
-        run(label, cfg, {k: (list(v) if isinstance(v, tuple) else v) for k, v in {**base, **kw}.items()}, seed,
-            surface_cloud(seed + 40, res, pts) + np.array([2, 0, 5], dtype=np.int32))
-    # the headline configuration at its real widths, from the reference's own YAML through its own config loader
-    from lib.config import Config as RefConfig
-    ref_cfg = RefConfig()
-    ref_cfg.merge_with_yaml(os.path.join(REF, 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'))
-    ref_cfg.check()
-    mc = ref_cfg.model
-    run('baseline_r1_yaml', mc, {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in vars(mc).items() if not k.startswith('_')}, 6,
-        surface_cloud(46, 256, 4000) + np.array([1, 4, 2], dtype=np.int32), {'yaml': 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'})
-    run('baseline_r1_yaml_12k', mc, {k: (list(v) if isinstance(v, (tuple, list)) else v) for k, v in vars(mc).items() if not k.startswith('_')}, 7,
-        surface_cloud(47, 256, 16000) + np.array([3, 1, 0], dtype=np.int32), {'yaml': 'config/convolutional/lossy_coord_v2/baseline_r1.yaml'})
-    return out
+    return run
 
 
 def make_codec_v2_partitions_chain():
@@ -1886,7 +1925,7 @@ def make_codec_color_chain():
 
 
 def main():
-    for name, fn in (('get_keep', make_get_keep), ('codec_lossl', make_codec_lossl), ('codec_color', make_codec_color), ('codec_v2', make_codec_v2), ('codec_v2_chain', make_codec_v2_chain), ('codec_v2_partitions_chain', make_codec_v2_partitions_chain), ('codec_color_chain', make_codec_color_chain), ('codec_color_partitions_chain', make_codec_color_partitions_chain), ('codec_int', make_codec_int), ('codec_v3', make_codec_v3), ('hilbert', make_hilbert), ('me_semantics', make_me_semantics), ('entropy_model_hyperprior', make_entropy_model_hyperprior), ('entropy_model_indexed', make_entropy_model_indexed), ('ptq_import', make_ptq_import), ('kdtree', make_kdtree), ('entropy_model', make_entropy_model), ('rans', make_rans), ('rans_random', make_rans_random), ('morton', make_morton), ('byteslist', make_byteslist), ('explut', make_explut)):
+    for name, fn in (('get_keep', make_get_keep), ('codec_lossl', make_codec_lossl), ('codec_color', make_codec_color), ('codec_v2', make_codec_v2), ('codec_v2_chain', make_codec_v2_chain), ('codec_v2_rates_chain', make_codec_v2_rates_chain), ('codec_v2_partitions_chain', make_codec_v2_partitions_chain), ('codec_color_chain', make_codec_color_chain), ('codec_color_partitions_chain', make_codec_color_partitions_chain), ('codec_int', make_codec_int), ('codec_v3', make_codec_v3), ('hilbert', make_hilbert), ('me_semantics', make_me_semantics), ('entropy_model_hyperprior', make_entropy_model_hyperprior), ('entropy_model_indexed', make_entropy_model_indexed), ('ptq_import', make_ptq_import), ('kdtree', make_kdtree), ('entropy_model', make_entropy_model), ('rans', make_rans), ('rans_random', make_rans_random), ('morton', make_morton), ('byteslist', make_byteslist), ('explut', make_explut)):
         if len(sys.argv) > 1 and name not in sys.argv[1:]:
             continue
         data = fn()

@@ -17,6 +17,19 @@ def test_builders_equal_the_reference_yaml(make, name):
     assert make() == ModelConfig.from_yaml(path)
 
 
+@pytest.mark.parametrize('name', ['baseline_kitti_r1', 'baseline_kitti_r3', 'baseline_kitti_r5'])
+def test_kitti_rate_points_of_the_gpu_test_equal_the_reference_yaml(name):
+    """the LiDAR rate points have no builder in model_config.py: tests/test_gpu_codec_v2_rates.py states their `model:` values, and this
+    holds them against the reference's files"""
+    from test_gpu_codec_v2_rates import KITTI
+    cfg = KITTI[name]()
+    assert len(cfg.compressed_channels) == len(cfg.geo_lossl_channels) == len(cfg.geo_lossl_if_sample) + 1
+    path = os.path.join(REF, name + '.yaml')
+    if not os.path.isfile(path):
+        pytest.skip('reference tree not present')
+    assert cfg == ModelConfig.from_yaml(path)
+
+
 def test_values_of_the_rate_points():
     r3, r5 = baseline_r3(), baseline_r5()
     assert r3.decoder_channels == (64, 16) and r3.encoder_channels == (16, 64, 128) and r3.skip_encoding_fea == -1

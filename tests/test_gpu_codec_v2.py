@@ -334,10 +334,12 @@ def test_deeper_lossy_part_keeps_local_maxima_of_the_decoder_input_cells(enc, de
     o = OracleV2(weights, cfg, conv='chain', order_fn=ME_order)
     want = o.compress(coords)
     assert data[:6 + 3 * (len(enc) - 1)] == want[:6 + 3 * (len(enc) - 1)]
+    # numerics version 3 specifies the logistic function: no arithmetic is left that the two sides do not share, so the bytes and the
+    # decoded point sets are EQUAL (tests/test_gpu_codec_v2_rates.py compares the stages' logits should this ever fail)
+    assert data == want
     rec_o = o.decompress(want)
     assert rec_o.shape == rec.shape
-    same = len({tuple(r) for r in rec.tolist()} & {tuple(r) for r in rec_o.tolist()})
-    assert same >= 0.995 * len(rec)            # identical up to threshold ties that fp32 exp rounding of the logits may flip
+    assert {tuple(r) for r in rec.tolist()} == {tuple(r) for r in rec_o.tolist()}
     pts = coords[:, 1:]                          # the cloud as coded (shifted); cells are aligned to its minimum corner
     lo, stages = pts.min(0), len(dec)
     assert {tuple(p) for p in ((rec - lo) >> stages).tolist()} == {tuple(p) for p in ((pts - lo) >> stages).tolist()}
@@ -383,12 +385,18 @@ def test_against_the_reference_run(run):
 
 def _chain_runs():
     """the chain-order reference runs of codec_v2_chain.json (round 4): the reference's model code over the stand-in engine with every
-    layer summed in the order the HIP kernels document -- two stand-in widths, and the real widths of baseline_r1.yaml on two clouds"""
+    layer summed in the order the HIP kernels document -- two stand-in widths, and the real widths of baseline_r1.yaml on two clouds;
+    and of codec_v2_rates_chain.json: the real widths of baseline_r3 / baseline_r5 / expanded_r3 / expanded_r5.yaml"""
     import json, os
-    with open(os.path.join(os.path.dirname(__file__), 'golden', 'codec_v2_chain.json')) as f:
-        g = json.load(f)
+    versions, runs = set(), []
+    for name in ('codec_v2_chain.json', 'codec_v2_rates_chain.json'):
+        with open(os.path.join(os.path.dirname(__file__), 'golden', name)) as f:
+            g = json.load(f)
+        versions.add(g['numerics_version'])
+        runs += g['runs']
+    assert len(versions) == 1, 'the two chain fixtures were generated under different numerics versions'
     keys = {f.name for f in __import__('dataclasses').fields(__import__('fastpcc_amd.codecs.lossy_coord_v2.model_config', fromlist=['ModelConfig']).ModelConfig)}
-    return g['numerics_version'], [dict(r, config={k: v for k, v in r['config'].items() if k in keys}) for r in g['runs']]
+    return versions.pop(), [dict(r, config={k: v for k, v in r['config'].items() if k in keys}) for r in runs]
 
 
 @pytest.mark.parametrize('run', _chain_runs()[1], ids=[r['label'] for r in _chain_runs()[1]])
@@ -402,7 +410,7 @@ def test_bytes_equal_the_reference_run_in_chain_order(run):
     from fastpcc_amd import hipops
     from fastpcc_amd.codecs.lossy_coord_v2 import Model
     from fastpcc_amd.codecs.lossy_coord_v2.model_config import ModelConfig
-    assert _chain_runs()[0] == hipops.numerics_version(), 'numerics version bumped: regenerate codec_v2_chain.json'
+    assert _chain_runs()[0] == hipops.numerics_version(), 'numerics version bumped: regenerate codec_v2_chain.json and codec_v2_rates_chain.json'
     cfg = ModelConfig(**{k: tuple(v) if isinstance(v, list) else v for k, v in run['config'].items()})
     torch.manual_seed(0)
     model = Model(cfg)

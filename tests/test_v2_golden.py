@@ -110,11 +110,15 @@ def test_oracle_pruning_rule_equals_the_reference_masks(case):
 # sides evaluate the same FMA chains in plain C.
 with open(os.path.join(os.path.dirname(__file__), 'golden', 'codec_v2_chain.json')) as f:
     GC = json.load(f)
+# the same at the real widths of the higher rate points (codec_v2_rates_chain.json): baseline_r3 / baseline_r5 (two and three decoder
+# stages), expanded_r3 / expanded_r5 (256-wide lossless pyramid), each YAML read by the reference's own loader
+with open(os.path.join(os.path.dirname(__file__), 'golden', 'codec_v2_rates_chain.json')) as f:
+    GR = json.load(f)
 
 
 def _chain_runs():
     keys = {f.name for f in __import__('dataclasses').fields(ModelConfig)}
-    return [dict(r, config={k: v for k, v in r['config'].items() if k in keys}) for r in GC['runs']]
+    return [dict(r, config={k: v for k, v in r['config'].items() if k in keys}) for r in GC['runs'] + GR['runs']]
 
 
 def recon_digest(points) -> str:
@@ -122,11 +126,23 @@ def recon_digest(points) -> str:
     return hashlib.sha256(np.sort((p[:, 0] << 42) | (p[:, 1] << 21) | p[:, 2]).tobytes()).hexdigest()
 
 
+def test_rate_point_runs_are_the_builders_configurations():
+    """what the reference's loader read from baseline_r3 / baseline_r5 / expanded_r3 / expanded_r5.yaml is what the builders of
+    model_config.py state (the GPU tests of these rate points build their models from the builders)"""
+    from fastpcc_amd.codecs.lossy_coord_v2 import model_config
+    runs = {r['label']: r for r in _chain_runs()}
+    for name in ('baseline_r3', 'baseline_r5', 'expanded_r3', 'expanded_r5'):
+        run = runs[name + '_yaml']
+        assert run['yaml'].endswith(f'/{name}.yaml')
+        assert ModelConfig(**{k: tuple(v) if isinstance(v, list) else v for k, v in run['config'].items()}) == getattr(model_config, name)()
+
+
 @pytest.mark.parametrize('run', _chain_runs(), ids=[r['label'] for r in _chain_runs()])
 def test_reference_run_in_chain_order(run):
     from fastpcc_amd import hipops
     from fastpcc_amd.engine import summation_order
     assert GC['numerics_version'] == hipops.numerics_version(), 'numerics version bumped: regenerate codec_v2_chain.json'
+    assert GR['numerics_version'] == hipops.numerics_version(), 'numerics version bumped: regenerate codec_v2_rates_chain.json'
     cfg, model = model_of(run)
     assert float(sum(p.detach().double().abs().sum() for n, p in model.named_parameters() if '.prior_' not in n)) == \
         pytest.approx(run['param_abs_sum'], rel=1e-12)
