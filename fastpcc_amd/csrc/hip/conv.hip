@@ -27,7 +27,7 @@
 // FPCC_NUMERICS_VERSION): the kernel offsets form four fixed groups, one wave of a workgroup each, partial sums added in group
 // order -- by four waves of a workgroup that meet in LDS (k_conv_wave<..., OG = 4>: maps below 100 K rows, which need the
 // parallelism) or by one wave that folds its accumulator into a running sum at every group boundary: k_conv_wave<..., FOLD>
-// (32-row units, three waves per SIMD) from 100 K rows, and k_conv_fold64 (64 x 64 units in which every A and B fragment feeds two
+// (32-row units, three waves per SIMD) from 100 K rows, and k_conv_wave64<.., FOLD> (64 x 64 units in which every A and B fragment feeds two
 // MFMAs, running sums in registers, two waves per SIMD) from 200 K rows on maps with a row order and 64 | 128 output channels.
 // All three leave the same bits.
 //
@@ -39,9 +39,6 @@
 // (256 B).  On the bench's 286 K .. 4.36 M-row maps the 64-row unit executes 2.2-2.6 % more pairs and the 27-offset launches take
 // about 3 % less time in all (per shape 2-6 % less; single launches between 6 % less and 2 % more): profiles/r07/fold64.md.
 #include "conv_common.h"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 
@@ -739,165 +736,17 @@ __global__ __launch_bounds__(256, ((FOLD || PERSIST || NAT) ? 3 : WaveCfg<NBW, C
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// 64 x 64 wave tile ("2 x 2"): the wave-autonomous kernel with TWO 32-row blocks and TWO 32-column blocks per wave.  Every A
+// 64 x 64 wave unit ("2 x 2"): the wave-autonomous kernel with TWO 32-row blocks and TWO 32-column blocks per wave.  Every A
 // fragment (16 bytes per lane, gathered) and every B fragment (16 bytes per lane, packed weights) feeds two MFMAs per k-step
-// instead of one resp. two: 4 vector-memory instructions per 16 MFMAs and 256 bytes of operands per MFMA, against 3 per 8 and
+// instead of one resp. two: 16 vector-memory instructions per 64 MFMAs and 256 bytes of operands per MFMA, against 12 per 32 and
 // 384 bytes in the 32 x 64 unit -- the operand stream out of L1 / L2, not the matrix pipe, is what bounds the 32 x 64 unit on the
 // large maps (profiles/r03/wave22_sweeps.md).  Four independent accumulators per wave.  The price: a 64-row unit executes every
 // kernel offset that any of its 64 rows has (in neighbour-pattern row order adjacent blocks have like patterns), and a
-// launch has half as many units -- so this tile is for maps with many row blocks.  Same FMA chain per output element (order 1).
-template <int SB>
-__global__ __launch_bounds__(256, 3) void k_conv_wave22(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_units) {
-    constexpr int CH = 32, G8 = 4;
-    __shared__ int32_t s_nbr_all[4][kMaxOffsets * 64];
-
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int li = lane & 31, lh = lane >> 5;
-    const unsigned n_cg = (unsigned)(nbt / 2);
-    const unsigned blk = a.row_order ? blockIdx.x : xcd_remap(blockIdx.x, gridDim.x);
-    const unsigned unit = blk * 4u + (unsigned)wv;
-    if (unit >= n_units) return;                    // no barrier below: a wave may leave on its own
-    const unsigned rb_ = unit / n_cg, cg = unit - rb_ * n_cg;
-    const int g = blockIdx.y;
-    const int64_t row0 = (int64_t)rb_ * 64;
-    const int c_in = a.c1 + a.c2;
-    const int n_chunks = c_in / CH;
-    int32_t *s_nbr = s_nbr_all[wv];
-
-    // lane = position `lane` of the unit's 64 rows here (one neighbour-table entry per lane and offset); in the MFMA phase lane
-    // (i, h) serves rows i (first block) and 32 + i (second block)
-    int32_t my_row = -1;
-    if (row0 + lane < a.n_out) my_row = a.row_order ? a.row_order[row0 + lane] : (int32_t)(row0 + lane);
-    // (a row-major table beside a row order holds its rows in position order: conv_common.h)
-    const int64_t table_row = (a.row_order && table_is_row_major(a)) ? row0 + lane : (int64_t)my_row;
-    unsigned wmask = 0;
-    for (int k = 0; k < a.n_off; ++k) {
-        int32_t v = -1;
-        if (my_row >= 0) v = a.nbr ? a.nbr[(int64_t)k * a.nbr_ks + table_row * a.nbr_os] : my_row;
-        s_nbr[k * 64 + lane] = v;
-        if (__ballot(v >= 0) != 0ull) wmask |= 1u << k;
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[rb][nb][r] = 0.0f;
-
-    const int n_stages = __popc(wmask) * n_chunks;
-    if (n_stages > 0) {
-        const int64_t chunk_floats = (int64_t)G8 * nbt * 256;
-        const float *wp_g = wp + (int64_t)g * a.n_off * n_chunks * chunk_floats + ((int64_t)cg * 2) * 256 + lane * 4;
-        const float *const zero = (const float *)g_zero_row + 4 * lh;
-        const float *const x1b = a.x1 + 4 * lh, *const x2b = a.x2 ? a.x2 + 4 * lh : zero;
-        const int64_t ld1 = a.ld1, ld2 = a.ld2;
-        const int n1 = a.c1 / CH;
-        const float *a1[2], *a2[2], *bpk;
-        int step[2];
-        auto set_offset = [&](int k) {
-#pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
-                const int32_t idx = s_nbr[k * 64 + 32 * rb + li];
-                const int32_t neg = idx >> 31;
-                const uint64_t m = (uint64_t)(int64_t)neg, z = reinterpret_cast<uint64_t>(zero) & m;
-                const int64_t row = idx & ~neg;
-                a1[rb] = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x1b + row * ld1) & ~m) | z);
-                a2[rb] = reinterpret_cast<const float *>((reinterpret_cast<uint64_t>(x2b + row * ld2) & ~m) | z);
-                step[rb] = CH & ~neg;
-            }
-            bpk = wp_g + (int64_t)k * n_chunks * chunk_floats;
-        };
-        unsigned rest = wmask;
-        int cc_f = 0;
-        set_offset(__ffs(rest) - 1);
-        const float *ap[2], *bp;
-        auto next_stage = [&]() {
-            const bool in1 = cc_f < n1;                           // wave-uniform
-            const int c = in1 ? cc_f : cc_f - n1;
-            ap[0] = (in1 ? a1[0] : a2[0]) + c * step[0];
-            ap[1] = (in1 ? a1[1] : a2[1]) + c * step[1];
-            bp = bpk + cc_f * chunk_floats;
-            if (cc_f + 1 < n_chunks) {
-                ++cc_f;
-            } else {
-                const unsigned r2 = rest & (rest - 1);
-                if (r2) { rest = r2; cc_f = 0; set_offset(__ffs(r2) - 1); }
-            }
-        };
-        f32x4 ra[2][G8], rbv[G8][2];
-        next_stage();
-#pragma unroll
-        for (int g8 = 0; g8 < G8; ++g8) {
-            __builtin_amdgcn_sched_barrier(0);
-            ra[0][g8] = *reinterpret_cast<const f32x4 *>(ap[0] + 8 * g8);
-            __builtin_amdgcn_sched_barrier(0);
-            ra[1][g8] = *reinterpret_cast<const f32x4 *>(ap[1] + 8 * g8);
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) {
-                __builtin_amdgcn_sched_barrier(0);
-                rbv[g8][nb] = *reinterpret_cast<const f32x4 *>(bp + ((int64_t)g8 * nbt + nb) * 256);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        for (int s = 0; s < n_stages; ++s) {
-            next_stage();                                       // stage s + 1
-            __builtin_amdgcn_sched_barrier(SB);
-#pragma unroll
-            for (int g8 = 0; g8 < G8; ++g8) {
-                const f32x4 av0 = ra[0][g8], av1 = ra[1][g8];
-                const f32x4 b0 = rbv[g8][0], b1 = rbv[g8][1];
-#define FPCC_STEP(c)                                                                                     \
-                acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0.c, b0.c, acc[0][0], 0, 0, 0);       \
-                acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av0.c, b1.c, acc[0][1], 0, 0, 0);       \
-                acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1.c, b0.c, acc[1][0], 0, 0, 0);       \
-                acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av1.c, b1.c, acc[1][1], 0, 0, 0);
-                FPCC_STEP(x) FPCC_STEP(y) FPCC_STEP(z) FPCC_STEP(w)
-#undef FPCC_STEP
-                __builtin_amdgcn_sched_barrier(SB);
-                ra[0][g8] = *reinterpret_cast<const f32x4 *>(ap[0] + 8 * g8);
-                __builtin_amdgcn_sched_barrier(SB);
-                ra[1][g8] = *reinterpret_cast<const f32x4 *>(ap[1] + 8 * g8);
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    __builtin_amdgcn_sched_barrier(SB);
-                    rbv[g8][nb] = *reinterpret_cast<const f32x4 *>(bp + ((int64_t)g8 * nbt + nb) * 256);
-                }
-                __builtin_amdgcn_sched_barrier(SB);
-            }
-        }
-    }
-
-    const float slope = (a.act == FPCC_ACT_PRELU && a.slope) ? a.slope[0] : 0.0f;
-    float bias2[2];
-#pragma unroll
-    for (int nb = 0; nb < 2; ++nb) bias2[nb] = a.bias ? a.bias[32 * ((int)cg * 2 + nb) + li] : 0.0f;
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) {
-        int64_t dsts[16];
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int64_t o = __shfl(my_row, 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh);
-            dsts[reg] = o < 0 ? -1 : a.out_map ? (int64_t)a.out_map[o * a.om_os + g * a.om_gs] : o * a.groups + g;
-        }
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-            const int64_t dst = dsts[reg];
-            if (dst < 0) continue;
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb)
-                a.out[dst * a.ldo + 32 * ((int)cg * 2 + nb) + li] = finish(acc[rb][nb][reg], bias2[nb], a.act, slope, a.clip);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Folded 64 x 64 wave unit: k_conv_wave22's operand path (every A and B fragment feeds two MFMAs: 16 vector-memory instructions per 64
-// MFMAs against 12 per 32 in the folded 32 x 64 unit) with the FOLD rule of k_conv_wave -- summation order 3 on ONE wave.  Four
-// accumulators and four running sums stay in registers (128 of the 256 a lane has at two waves per SIMD; operands 64, addresses ~25).
-//
+// launch has half as many units -- so this unit is for maps with many row blocks.
+// !FOLD: the order-1 chain, groups and out_map as in k_conv_wave, three waves per SIMD (launch_wave22, knob 9).  FOLD: the FOLD rule of
+// k_conv_wave -- summation order 3 on ONE wave; four accumulators and four running sums stay in registers (128 of the 256 a lane has at
+// two waves per SIMD; operands 64, addresses ~25); one group, no output map (launch_fold64: large maps with a row order).  Profile
+// notes up to round 14 call the folded instantiation k_conv_fold64 and the plain one k_conv_wave22.
 // The fold boundaries are those of the UNIT's offset mask (the union over its two 32-row blocks), not of each block's own.  That
 // leaves the bits of the 32-row folded kernel, block by block:
 //   * an offset only the other block has: this block's rows read the zero row, every term is fma(0, w, acc) == acc -- the case a
@@ -906,13 +755,12 @@ __global__ __launch_bounds__(256, 3) void k_conv_wave22(ConvArgs a, const float 
 //     stays +0, and the unit folds t = t + (+0) (t = +0 for the first group) -- exactly fold_zero of the 32-row kernel;
 //   * a group neither block has: fold_zero for both, as in the 32-row kernel.
 // So per block and group the running sum receives either the block's own order-1 partial sum or +0, in group order.
-// The price: a unit executes every offset either of its blocks has (pattern row order puts like blocks side by side), and a launch
-// has half as many units -- for large maps with a row order (launch_grouped).
 // (Leaving out the MFMAs of a block that lacks the stage's offset -- scalar branches around them, loads unconditional -- compiles without
 // scratch or vmcnt(0), but the 27-offset launches on maps >= 200 K rows took 1.3-2.5 % MORE time with it: profiles/r08/discarded_work.md.)
-__global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_units) {
+// SB: sched_barrier mask of the stage loop as in k_conv_wave (0x6: the next stage's address arithmetic may float between the MFMAs).
+template <int SB, bool FOLD>
+__global__ __launch_bounds__(256, FOLD ? 2 : 3) void k_conv_wave64(ConvArgs a, const float *__restrict__ wp, int nbt, unsigned n_units) {
     constexpr int CH = 32, G8 = 4;
-    constexpr int SB = 0x6;                         // the next stage's address arithmetic may float between the MFMAs (k_conv_wave)
     __shared__ int32_t s_nbr_all[4][kMaxOffsets * 64];
 
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: see k_conv_wave)
@@ -922,6 +770,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
     const unsigned unit = blk * 4u + (unsigned)wv;
     if (unit >= n_units) return;                    // no barrier below: a wave may leave on its own
     const unsigned rb_ = unit / n_cg, cg = unit - rb_ * n_cg;
+    const int g = FOLD ? 0 : blockIdx.y;
     const int64_t row0 = (int64_t)rb_ * 64;
     const int c_in = a.c1 + a.c2;
     const int n_chunks = c_in / CH;
@@ -951,7 +800,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
                 if (__ballot(v >= 0) != 0ull) wmask |= 1u << k;
             }
     } else {
-        for (int k = 0; k < n_off; ++k) {
+        for (int k = 0; k < n_off; ++k) {                 // (a multi-offset call always brings a table: fpcc_conv_f32_pk)
             int32_t v = -1;
             if (my_row >= 0) v = a.nbr[(int64_t)k * a.nbr_ks + (int64_t)my_row * a.nbr_os];
             s_nbr[k * 64 + lane] = v;
@@ -969,7 +818,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[rb][nb][r] = 0.0f;
 
-    // running sum over the offset groups finished so far (n_folded of them): fold_acc / fold_zero of k_conv_wave, for four accumulators
+    // FOLD: running sum over the offset groups finished so far (n_folded of them): fold_acc / fold_zero of k_conv_wave, for four
+    // accumulators (the plain form never calls them and leaves tsum untouched)
     int n_folded = 0, cur_g = 0;
     auto fold_acc = [&]() {
 #pragma unroll
@@ -994,7 +844,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
     };
     unsigned rest_c = wmask;
     int cc_c = 0;
-    if (wmask) {
+    if (FOLD && wmask) {
         cur_g = offset_group_of(__ffs(wmask) - 1, n_off);
         for (int gz = 0; gz < cur_g; ++gz) fold_zero();
     }
@@ -1002,7 +852,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
     const int n_stages = __popc(wmask) * n_chunks;
     if (n_stages > 0) {
         const int64_t chunk_floats = (int64_t)G8 * nbt * 256;
-        const float *wp_g = wp + ((int64_t)cg * 2) * 256 + lane * 4;
+        const float *wp_g = wp + (FOLD ? 0 : (int64_t)g * n_off * n_chunks * chunk_floats) + ((int64_t)cg * 2) * 256 + lane * 4;
         const float *const zero = (const float *)g_zero_row + 4 * lh;
         const float *const x1b = a.x1 + 4 * lh, *const x2b = a.x2 ? a.x2 + 4 * lh : zero;
         const int64_t ld1 = a.ld1, ld2 = a.ld2;
@@ -1055,16 +905,18 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
         }
         __builtin_amdgcn_sched_barrier(0);
         for (int s = 0; s < n_stages; ++s) {
-            // compute position (one stage behind the fetch position): entering the first chunk of an offset of a later group
-            if (cc_c == 0) {
-                const int gk = offset_group_of(__ffs(rest_c) - 1, n_off);
-                if (gk != cur_g) {
-                    fold_acc();
-                    for (int gz = cur_g + 1; gz < gk; ++gz) fold_zero();
-                    cur_g = gk;
+            if (FOLD) {
+                // compute position (one stage behind the fetch position): entering the first chunk of an offset of a later group
+                if (cc_c == 0) {
+                    const int gk = offset_group_of(__ffs(rest_c) - 1, n_off);
+                    if (gk != cur_g) {
+                        fold_acc();
+                        for (int gz = cur_g + 1; gz < gk; ++gz) fold_zero();
+                        cur_g = gk;
+                    }
                 }
+                if (++cc_c == n_chunks) { cc_c = 0; rest_c &= rest_c - 1; }
             }
-            if (++cc_c == n_chunks) { cc_c = 0; rest_c &= rest_c - 1; }
             next_stage();                                       // stage s + 1
             __builtin_amdgcn_sched_barrier(SB);
 #pragma unroll
@@ -1091,8 +943,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
             }
         }
     }
-    if (wmask) { fold_acc(); ++cur_g; }
-    for (int gz = cur_g; gz < 4; ++gz) fold_zero();
+    if (FOLD) {
+        if (wmask) { fold_acc(); ++cur_g; }
+        for (int gz = cur_g; gz < 4; ++gz) fold_zero();
+    }
 
     const float slope = (a.act == FPCC_ACT_PRELU && a.slope) ? a.slope[0] : 0.0f;
     float bias2[2];
@@ -1104,7 +958,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             const int64_t o = __shfl(my_row, 32 * rb + (reg & 3) + 8 * (reg >> 2) + 4 * lh);
-            dsts[reg] = o < 0 ? -1 : o;             // grouped shapes: one group, no output map
+            // (FOLD: grouped shapes have one group and no output map)
+            dsts[reg] = o < 0 ? -1 : FOLD ? o : a.out_map ? (int64_t)a.out_map[o * a.om_os + g * a.om_gs] : o * a.groups + g;
         }
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
@@ -1112,14 +967,17 @@ __global__ __launch_bounds__(256, 2) void k_conv_fold64(ConvArgs a, const float 
             if (dst < 0) continue;
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
-                a.out[dst * a.ldo + 32 * ((int)cg * 2 + nb) + li] = finish(tsum[rb][nb][reg], bias2[nb], a.act, slope, a.clip);
+                a.out[dst * a.ldo + 32 * ((int)cg * 2 + nb) + li] = finish(FOLD ? tsum[rb][nb][reg] : acc[rb][nb][reg], bias2[nb], a.act, slope, a.clip);
         }
     }
 }
 
+// one thread per packed element: [m][cc][g8][nb][h][i][j] <- w[m][32 cc + 8 g8 + 4 h + j][32 nb + i]; NAT, the natural-order image
+// (k_conv_wave<..., NAT>): <- w[m][32 cc + 8 g8 + 2 j + h][32 nb + i] -- a lane's 16-byte piece is j = 0 .. 3 of its half h, in MFMA
+// issue order
+template <bool NAT>
 __global__ __launch_bounds__(256) void k_pack_weights(const float *__restrict__ w, int64_t n_mats, int c_in, int c_out,
                                                       float *__restrict__ wp) {
-    // one thread per packed element: [m][cc][g8][nb][h][i][j] <- w[m][32 cc + 8 g8 + 4 h + j][32 nb + i]
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int64_t per_mat = (int64_t)c_in * c_out;
     if (e >= n_mats * per_mat) return;
@@ -1132,26 +990,7 @@ __global__ __launch_bounds__(256) void k_pack_weights(const float *__restrict__ 
     const int nb = (int)(r % nbt); r /= nbt;
     const int g8 = (int)(r & 3); r >>= 2;
     const int cc = (int)r;
-    wp[e] = w[m * per_mat + (int64_t)(32 * cc + 8 * g8 + 4 * h + j) * c_out + 32 * nb + i];
-}
-
-// the natural-order image (k_conv_wave<..., NAT>): [m][cc][g8][nb][h][i][j] <- w[m][32 cc + 8 g8 + 2 j + h][32 nb + i] -- a lane's 16-byte
-// piece is j = 0 .. 3 of its half h, in MFMA issue order
-__global__ __launch_bounds__(256) void k_pack_weights_nat(const float *__restrict__ w, int64_t n_mats, int c_in, int c_out,
-                                                          float *__restrict__ wp) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t per_mat = (int64_t)c_in * c_out;
-    if (e >= n_mats * per_mat) return;
-    const int nbt = c_out / 32;
-    const int64_t m = e / per_mat;
-    int64_t r = e - m * per_mat;
-    const int j = (int)(r & 3); r >>= 2;
-    const int i = (int)(r & 31); r >>= 5;
-    const int h = (int)(r & 1); r >>= 1;
-    const int nb = (int)(r % nbt); r /= nbt;
-    const int g8 = (int)(r & 3); r >>= 2;
-    const int cc = (int)r;
-    wp[e] = w[m * per_mat + (int64_t)(32 * cc + 8 * g8 + 2 * j + h) * c_out + 32 * nb + i];
+    wp[e] = w[m * per_mat + (int64_t)(32 * cc + 8 * g8 + (NAT ? 2 * j : 4 * h) + (NAT ? h : j)) * c_out + 32 * nb + i];
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -1231,12 +1070,22 @@ __global__ __launch_bounds__(256) void k_conv_c1_pointwise(ConvArgs a) {
     a.out[o * a.ldo + j] = finish(fmaf(a.x1[o * a.ld1], a.w[j], 0.0f), a.bias ? a.bias[j] : 0.0f, a.act, slope, a.clip);
 }
 
+// Work units of a wave-kernel launch: (blocks of unit_rows output rows) x (column groups), one wave -- or, grouped, one workgroup --
+// each.  Returns their number, or -1 with the error set when it does not fit the kernels' unit index.
+inline int64_t wave_units(const ConvArgs &a, int unit_rows, int col_groups) {
+    const int64_t units = (a.n_out + unit_rows - 1) / unit_rows * col_groups;
+    if (units <= 0x7fffffffll) return units;
+    fail_arg("conv_f32: too many work units");
+    return -1;
+}
+// four one-wave units per workgroup
+inline dim3 wave_grid(int64_t units, int groups) { return dim3((unsigned)((units + 3) / 4), groups); }
+
 template <int NBW>
 int launch_wave_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
-    const int64_t row_blocks = (a.n_out + 31) / 32;
-    const int64_t units = row_blocks * (nbt / NBW);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
-    const dim3 grid((unsigned)((units + 3) / 4), a.groups);
+    const int64_t units = wave_units(a, 32, nbt / NBW);
+    if (units < 0) return FPCC_E_ARG;
+    const dim3 grid = wave_grid(units, a.groups);
     // knob FPCC_WAVE_SB=1: the address arithmetic of the next stage may be scheduled between the MFMAs
     if (knob(kKnobWaveSb)) hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     else hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
@@ -1301,9 +1150,8 @@ inline bool persist_ok(const ConvArgs &a) {
 // Grouped evaluation (summation order 3): one workgroup per (32-row block, column group), its four waves = the four offset groups.
 template <int NBW>
 int launch_grouped_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
-    const int64_t row_blocks = (a.n_out + 31) / 32;
-    const int64_t units = row_blocks * (nbt / NBW);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
+    const int64_t units = wave_units(a, 32, nbt / NBW);
+    if (units < 0) return FPCC_E_ARG;
     const bool stamps = knob(kKnobStamps) != 0;
     const int64_t slots = persist_slots();
     if (!stamps && persist_ok(a) && units > slots) {
@@ -1324,8 +1172,8 @@ int launch_grouped_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t 
 // Folded evaluation of the same order (FOLD): one wave per unit, for maps with at least kKnobGroupedFoldRows rows.
 template <int NBW>
 int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
-    const int64_t units = ((a.n_out + 31) / 32) * (nbt / NBW);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
+    const int64_t units = wave_units(a, 32, nbt / NBW);
+    if (units < 0) return FPCC_E_ARG;
     const int64_t slots = persist_slots();
     if (!knob(kKnobStamps) && persist_ok(a) && (units + 3) / 4 > slots) {
         int rc = FPCC_OK;
@@ -1335,12 +1183,11 @@ int launch_folded_cfg(const ConvArgs &a, const float *wp, int nbt, hipStream_t s
                            counter);
         return check_hip(hipGetLastError(), "k_conv_wave(folded, persistent)");
     }
-    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a, wp, nbt,
-                       (unsigned)units);
+    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, true>), wave_grid(units, a.groups), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     return check_hip(hipGetLastError(), "k_conv_wave(folded)");
 }
 
-// Folded 64 x 64 wave units (k_conv_fold64) for the folded launches of the shapes they were measured on -- 27 offsets (3x3x3) or 8
+// Folded 64 x 64 wave units (k_conv_wave64<0x6, true>) for the folded launches of the shapes they were measured on -- 27 offsets (3x3x3) or 8
 // (stride-2 2x2x2, profiles/r07/fold64.md section 4), 64 | 128 output channels: knob 13 / FPCC_CONV_FOLD64 = 0: on maps with a row order (pattern order puts like blocks side by side) of at
 // least kFold64Rows rows, 1: never (the 32-row folded units), 2: on every folded launch of such a shape.  Every other shape, maps
 // without a row order and the persistent folded form (knob 12) keep the 32-row units.
@@ -1356,11 +1203,11 @@ inline bool use_fold64(const ConvArgs &a, int nbt) {
 }
 
 int launch_fold64(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
-    const int64_t units = ((a.n_out + 63) / 64) * (nbt / 2);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
-    hipLaunchKernelGGL(k_conv_fold64, dim3((unsigned)((units + 3) / 4), 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    const int64_t units = wave_units(a, 64, nbt / 2);
+    if (units < 0) return FPCC_E_ARG;
+    hipLaunchKernelGGL((k_conv_wave64<0x6, true>), wave_grid(units, 1), dim3(256), 0, s, a, wp, nbt, (unsigned)units);
     g_fold64_launches.fetch_add(1, std::memory_order_relaxed);
-    return check_hip(hipGetLastError(), "k_conv_fold64");
+    return check_hip(hipGetLastError(), "k_conv_wave64(folded)");
 }
 
 int launch_grouped(const ConvArgs &a, const float *wp, hipStream_t s) {
@@ -1382,20 +1229,21 @@ int launch_grouped(const ConvArgs &a, const float *wp, hipStream_t s) {
     return nbw == 2 ? launch_grouped_cfg<2>(a, wp, nbt, s) : launch_grouped_cfg<1>(a, wp, nbt, s);
 }
 
+// the plain 64 x 64 unit (k_conv_wave64<SB, false>): order 1, groups and output maps as in k_conv_wave
+int launch_wave22(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
+    const int64_t units = wave_units(a, 64, nbt / 2);
+    if (units < 0) return FPCC_E_ARG;
+    const dim3 grid = wave_grid(units, a.groups);
+    if (knob(kKnobWaveSb)) hipLaunchKernelGGL((k_conv_wave64<0x6, false>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    else hipLaunchKernelGGL((k_conv_wave64<0, false>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
+    return check_hip(hipGetLastError(), "k_conv_wave64");
+}
+
 // Unit width (column blocks per wave) by map size, measured on MI355X (profiles/r02/wave_kernel_sweeps.md): two column blocks
 // from 32 Ki rows up, one below -- on a 18 K-row map one-block units are 20 % faster (4x the units for the same chip), on
 // 272 K rows two-block units gather every row half as often.  Four-block units (every row gathered once) are never the
 // fastest: the B stream is 256 bytes per MFMA at any width, and three waves per SIMD hide less than five.
 // Knob FPCC_WAVE_NBW = 1|2|4 forces.
-int launch_wave22(const ConvArgs &a, const float *wp, int nbt, hipStream_t s) {
-    const int64_t units = ((a.n_out + 63) / 64) * (nbt / 2);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
-    const dim3 grid((unsigned)((units + 3) / 4), a.groups);
-    if (knob(kKnobWaveSb)) hipLaunchKernelGGL((k_conv_wave22<0x6>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    else hipLaunchKernelGGL((k_conv_wave22<0>), grid, dim3(256), 0, s, a, wp, nbt, (unsigned)units);
-    return check_hip(hipGetLastError(), "k_conv_wave22");
-}
-
 int launch_wave(const ConvArgs &a, const float *wp, hipStream_t s) {
     const int nbt = a.c_out / 32;
     const int64_t work = a.n_out * a.groups;
@@ -1410,7 +1258,6 @@ int launch_wave(const ConvArgs &a, const float *wp, hipStream_t s) {
     return launch_wave_cfg<1>(a, wp, nbt, s);
 }
 
-
 // Natural-order matrix path (summation order 0; natural_shape()): knob 15 / FPCC_CONV_NATURAL_MFMA = 0: these shapes on k_conv_valu,
 // 1: on k_conv_wave<..., NAT>, 2 (default): on the matrix kernel from kNaturalMfmaRows output rows (rows x groups), k_conv_valu below.
 // Result-neutral: both kernels evaluate the same chain.  Threshold and unit widths: profiles/r09/expanded.md.
@@ -1424,10 +1271,10 @@ inline bool use_natural_mfma(int64_t work) {
 template <int NBW>
 int launch_natural_cfg(const ConvArgs &a, const float *wp, hipStream_t s) {
     constexpr int nbt = 8;
-    const int64_t units = ((a.n_out + 31) / 32) * (nbt / NBW);
-    if (units > 0x7fffffffll) return fail_arg("conv_f32: too many work units");
-    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, false, false, true>), dim3((unsigned)((units + 3) / 4), a.groups), dim3(256), 0, s, a,
-                       wp, nbt, (unsigned)units);
+    const int64_t units = wave_units(a, 32, nbt / NBW);
+    if (units < 0) return FPCC_E_ARG;
+    hipLaunchKernelGGL((k_conv_wave<NBW, 32, 0x6, false, 1, false, false, true>), wave_grid(units, a.groups), dim3(256), 0, s, a, wp, nbt,
+                       (unsigned)units);
     g_natural_launches.fetch_add(1, std::memory_order_relaxed);
     return check_hip(hipGetLastError(), "k_conv_wave(natural)");
 }
@@ -1590,7 +1437,6 @@ int launch_pointwise(const ConvArgs &a, const float *wp, hipStream_t s) {
         default: return -1;
     }
 }
-
 
 // 3x3x3 convolution of a CONSTANT-ONE one-channel input (the codec's first layer: every voxel carries the feature 1): the sum
 // over the neighbours that exist of w[k][j], in ascending offset order -- the same chain the general kernel evaluates with
@@ -1790,7 +1636,7 @@ extern "C" int fpcc_conv_pack_weights_nat_f32(const float *w, int64_t n_mats, in
         return fail_arg("conv_pack_weights_nat: c_in must be a multiple of 32 (<= 512) and c_out 256");
     if (n_mats == 0) return FPCC_OK;
     if (!w || !w_packed) return fail_arg("conv_pack_weights_nat: null pointer");
-    hipLaunchKernelGGL(k_pack_weights_nat, dim3(blocks_for(n_mats * c_in * c_out, 256)), dim3(256), 0, as_stream(stream), w, n_mats,
+    hipLaunchKernelGGL(k_pack_weights<true>, dim3(blocks_for(n_mats * c_in * c_out, 256)), dim3(256), 0, as_stream(stream), w, n_mats,
                        c_in, c_out, w_packed);
     return check_hip(hipGetLastError(), "k_pack_weights_nat");
 }
@@ -1800,7 +1646,7 @@ extern "C" int fpcc_conv_pack_weights_f32(const float *w, int64_t n_mats, int c_
         return fail_arg("conv_pack_weights: c_in must be a multiple of 32 and c_out one of 32, 64, 128");
     if (n_mats == 0) return FPCC_OK;
     if (!w || !w_packed) return fail_arg("conv_pack_weights: null pointer");
-    hipLaunchKernelGGL(k_pack_weights, dim3(blocks_for(n_mats * c_in * c_out, 256)), dim3(256), 0, as_stream(stream), w, n_mats,
+    hipLaunchKernelGGL(k_pack_weights<false>, dim3(blocks_for(n_mats * c_in * c_out, 256)), dim3(256), 0, as_stream(stream), w, n_mats,
                        c_in, c_out, w_packed);
     return check_hip(hipGetLastError(), "k_pack_weights");
 }
@@ -1919,316 +1765,6 @@ extern "C" int fpcc_conv_f32_pk(const float *x1, int c1, int ld1, const float *x
     if (c_out <= 4) return launch_valu<4>(a, s);
     if (c_out <= 8) return launch_valu<8>(a, s);
     return launch_valu<16>(a, s);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Row order for the MFMA tiles.  A 32-row MFMA block executes every kernel offset that ANY of its rows has; in Morton
-// order a block of 32 surface voxels has ~24 of the 27 offsets between them although each row has only ~13, so the
-// kernel runs ~1.8x the algorithmic flop.  Sorting the rows of a window of 2^window_log2 consecutive rows by their
-// 27-bit neighbour-presence pattern (ranked as a Gray code, so that consecutive patterns differ in few bits) puts rows
-// with like patterns into the same block: ~15-16 offsets per block.  Windows keep the gathers inside an L2-sized
-// neighbourhood.  Results do not depend on the order (every output row is its own summation chain).
-namespace fpcc {
-namespace {
-__global__ void k_conv_row_keys(const int32_t *__restrict__ nbr, int n_off, int64_t nbr_ks, int64_t nbr_os, int64_t n,
-                                int window_log2, int64_t *__restrict__ keys, uint32_t *__restrict__ masks) {
-    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= n) return;
-    uint32_t m = 0;
-    for (int k = 0; k < n_off; ++k) m |= (nbr[(int64_t)k * nbr_ks + o * nbr_os] >= 0 ? 1u : 0u) << k;
-    if (masks) masks[o] = m;
-    // rank of m in the binary-reflected Gray sequence
-    m ^= m >> 1; m ^= m >> 2; m ^= m >> 4; m ^= m >> 8; m ^= m >> 16;
-    keys[o] = ((o >> window_log2) << 32) | (int64_t)m;
-}
-
-// the same keys from the rows' presence masks (written by the table's producer: fpcc_nbr27_from_parent_ex) -- 4 bytes read per row
-// instead of the row's 27 table entries
-__global__ void k_conv_row_keys_masks(const uint32_t *__restrict__ masks, int64_t n, int window_log2, int64_t *__restrict__ keys) {
-    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= n) return;
-    uint32_t m = masks[o];
-    m ^= m >> 1; m ^= m >> 2; m ^= m >> 4; m ^= m >> 8; m ^= m >> 16;
-    keys[o] = ((o >> window_log2) << 32) | (int64_t)m;
-}
-
-// rows of a row-major table in position order: out[p] = rows[order[p]], whole 16-byte pieces (ld / 4 per row): eight consecutive lanes
-// move one 128-byte line, a wave's loads are eight scattered lines, its stores 1 KB contiguous
-__global__ __launch_bounds__(256) void k_gather_table_rows(const int4 *__restrict__ rows, const int32_t *__restrict__ order, int64_t n,
-                                                           int pieces, int4 *__restrict__ out) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= n * pieces) return;
-    const int64_t p = e / pieces;
-    const int j = (int)(e - p * pieces);
-    out[e] = rows[(int64_t)order[p] * pieces + j];
-}
-
-// one wave per group of `group` (<= 64) consecutive positions of row_order: key = (offsets the group lacks) << 32 | group
-__global__ __launch_bounds__(256) void k_conv_tile_keys(const uint32_t *__restrict__ row_masks, int n_off,
-                                                        const int32_t *__restrict__ row_order, int64_t n, int group,
-                                                        int64_t n_groups, int64_t *__restrict__ keys) {
-    const int64_t g = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (g >= n_groups) return;
-    const int64_t pos = g * group + lane;
-    uint32_t m = 0;
-    if (lane < group && pos < n) m = row_masks[row_order ? (int64_t)row_order[pos] : pos];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o);
-    if (lane == 0) keys[g] = ((int64_t)(n_off - __popc(m)) << 32) | g;
-}
-
-// Permutation that sorts <= 16384 group keys (fpcc_conv_tile_keys: (lacking offsets) << 32 | group) -- i.e. a STABLE counting sort
-// of the groups by their <= 33 possible weights.  One workgroup, three barriers; replaces a 64-bit merge sort of ~10 launches
-// per coordinate map (rocprim sorts arrays this small with block sort + log2(n / block) merge passes).
-template <int kPer>
-__global__ __launch_bounds__(1024) void k_group_counting_order(const int64_t *__restrict__ keys, int n, int32_t *__restrict__ perm) {
-    constexpr int kBins = 34;
-    __shared__ uint16_t s_wave[16][kBins];
-    __shared__ uint32_t s_base[kBins];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int per = (n + 1023) / 1024;                           // consecutive groups per thread (<= kPer)
-    const int g0 = t * per;
-    uint8_t bin[kPer];
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        const int g = g0 + j;
-        bin[j] = (j < per && g < n) ? (uint8_t)min((int)(keys[g] >> 32), kBins - 1) : 255;
-    }
-    uint16_t before[kBins];                                      // groups of this bin in earlier threads of my wave
-#pragma unroll
-    for (int b = 0; b < kBins; ++b) {
-        int c = 0;
-#pragma unroll
-        for (int j = 0; j < kPer; ++j) c += bin[j] == b;
-        int incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int up = __shfl_up(incl, o);
-            if (lane >= o) incl += up;
-        }
-        before[b] = (uint16_t)(incl - c);
-        if (lane == 63) s_wave[wv][b] = (uint16_t)incl;
-    }
-    __syncthreads();
-    if (t < kBins) {                                             // per bin: exclusive prefix over the 16 waves, and the bin's total
-        uint32_t run = 0;
-        for (int w = 0; w < 16; ++w) { const uint32_t c = s_wave[w][t]; s_wave[w][t] = (uint16_t)run; run += c; }
-        s_base[t] = run;
-    }
-    __syncthreads();
-    if (t == 0) {
-        uint32_t run = 0;
-        for (int b = 0; b < kBins; ++b) { const uint32_t c = s_base[b]; s_base[b] = run; run += c; }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < kPer; ++j) {
-        if (bin[j] == 255) continue;
-        uint32_t pos = 0;
-#pragma unroll
-        for (int b = 0; b < kBins; ++b)
-            if (bin[j] == b) { pos = s_base[b] + s_wave[wv][b] + before[b]; before[b] += 1; }
-        perm[pos] = g0 + j;
-    }
-}
-
-__global__ void k_conv_regroup_rows(const int32_t *__restrict__ row_order, const int32_t *__restrict__ group_perm, int64_t n,
-                                    int group, int64_t n_groups, int32_t *__restrict__ out) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const int64_t g = p / group;
-    const int64_t src = g < n_groups ? (int64_t)group_perm[g] * group + (p - g * group) : p;    // the ragged tail stays last
-    out[p] = row_order ? row_order[src] : (int32_t)src;
-}
-}  // namespace
-}  // namespace fpcc
-
-extern "C" int fpcc_conv_tile_keys(const uint32_t *row_masks, int n_offsets, const int32_t *row_order, int64_t n, int group,
-                                   int64_t *keys_out, void *stream) {
-    if (n < 0 || n_offsets < 1 || n_offsets > 32 || group < 1 || group > 64) return fail_arg("conv_tile_keys: sizes out of range");
-    const int64_t n_groups = n / group;
-    if (n_groups == 0) return FPCC_OK;
-    if (!row_masks || !keys_out) return fail_arg("conv_tile_keys: null pointer");
-    hipLaunchKernelGGL(k_conv_tile_keys, dim3(blocks_for(n_groups, 4)), dim3(256), 0, as_stream(stream), row_masks, n_offsets,
-                       row_order, n, group, n_groups, keys_out);
-    return check_hip(hipGetLastError(), "k_conv_tile_keys");
-}
-
-extern "C" int fpcc_conv_group_order(const int64_t *group_keys, int64_t n_groups, int32_t *perm_out, void *stream) {
-    if (n_groups < 0 || n_groups > 16384) return fail_arg("conv_group_order: at most 16384 groups");
-    if (n_groups == 0) return FPCC_OK;
-    if (!group_keys || !perm_out) return fail_arg("conv_group_order: null pointer");
-    const int per = (int)((n_groups + 1023) / 1024);
-    if (per <= 2) hipLaunchKernelGGL(k_group_counting_order<2>, dim3(1), dim3(1024), 0, as_stream(stream), group_keys, (int)n_groups, perm_out);
-    else if (per <= 5) hipLaunchKernelGGL(k_group_counting_order<5>, dim3(1), dim3(1024), 0, as_stream(stream), group_keys, (int)n_groups, perm_out);
-    else hipLaunchKernelGGL(k_group_counting_order<16>, dim3(1), dim3(1024), 0, as_stream(stream), group_keys, (int)n_groups, perm_out);
-    return check_hip(hipGetLastError(), "k_group_counting_order");
-}
-
-extern "C" int fpcc_conv_regroup_rows(const int32_t *row_order, const int32_t *group_perm, int64_t n, int group,
-                                      int32_t *row_order_out, void *stream) {
-    if (n < 0 || group < 1) return fail_arg("conv_regroup_rows: sizes out of range");
-    if (n == 0) return FPCC_OK;
-    if (!row_order_out || (n / group > 0 && !group_perm)) return fail_arg("conv_regroup_rows: null pointer");
-    hipLaunchKernelGGL(k_conv_regroup_rows, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), row_order, group_perm, n,
-                       group, n / group, row_order_out);
-    return check_hip(hipGetLastError(), "k_conv_regroup_rows");
-}
-
-extern "C" int fpcc_conv_row_keys_masks(const uint32_t *masks, int64_t n, int window_log2, int64_t *keys_out, void *stream) {
-    if (n < 0 || window_log2 < 5 || window_log2 > 31) return fail_arg("conv_row_keys_masks: bad sizes");
-    if (n == 0) return FPCC_OK;
-    if (!masks || !keys_out) return fail_arg("conv_row_keys_masks: null pointer");
-    hipLaunchKernelGGL(k_conv_row_keys_masks, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), masks, n, window_log2, keys_out);
-    return check_hip(hipGetLastError(), "k_conv_row_keys_masks");
-}
-
-extern "C" int fpcc_gather_table_rows_i32(const int32_t *rows, int ld, const int32_t *order, int64_t n, int32_t *out, void *stream) {
-    if (n < 0 || ld < 4 || ld % 4) return fail_arg("gather_table_rows: ld must be a positive multiple of 4");
-    if (n == 0) return FPCC_OK;
-    if (!rows || !order || !out || !aligned16(rows) || !aligned16(out)) return fail_arg("gather_table_rows: null or unaligned pointer");
-    hipLaunchKernelGGL(k_gather_table_rows, dim3(blocks_for(n * (ld / 4), 256)), dim3(256), 0, as_stream(stream),
-                       reinterpret_cast<const int4 *>(rows), order, n, ld / 4, reinterpret_cast<int4 *>(out));
-    return check_hip(hipGetLastError(), "k_gather_table_rows");
-}
-
-extern "C" int fpcc_conv_row_keys(const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os, int64_t n,
-                                  int window_log2, int64_t *keys_out, uint32_t *masks_out, void *stream) {
-    if (n < 0 || n_offsets < 1 || n_offsets > 32 || window_log2 < 5 || window_log2 > 30)
-        return fail_arg("conv_row_keys: sizes out of range");
-    if (n == 0) return FPCC_OK;
-    if (!nbr || !keys_out) return fail_arg("conv_row_keys: null pointer");
-    hipLaunchKernelGGL(k_conv_row_keys, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), nbr, n_offsets, nbr_ks,
-                       nbr_os, n, window_log2, keys_out, masks_out);
-    return check_hip(hipGetLastError(), "k_conv_row_keys");
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Row order in whole units (fpcc_conv_row_order_units).  The windowed order above ends every (window, pattern) run whose length is no
-// multiple of the unit height in a unit of two patterns, which executes the union of both for all its rows: on a batch-sized map a
-// quarter of the rows sit in such units and the 64-row units execute 1.057x the (row, offset) pairs the rows have.  Here the whole
-// units of every run stay where they are and the tails of ALL windows are pooled and sorted by pattern: the executed pairs of a
-// whole-map sort (1.012x at 4.36 M rows) with three quarters of the rows still window-local.
-namespace fpcc {
-namespace {
-__device__ __forceinline__ uint32_t gray_rank(uint32_t m) {
-    m ^= m >> 1; m ^= m >> 2; m ^= m >> 4; m ^= m >> 8; m ^= m >> 16;
-    return m;
-}
-
-// The two sorts of the specification (by (window, rank), then by whole ? 0 : 1 + rank) are done in the other order, which gives the
-// same permutation with fewer sort passes.  A stable sort by RANK alone leaves the rows (rank, position)-ordered: the runs of equal
-// (rank, window) are contiguous in it as well, with the same rows in the same (position) order, so "whole" is the same predicate;
-// and the tails are then already in their final order -- by rank, inside a rank by window and position.  A second stable sort by
-// key2 = whole ? window : n_windows moves the whole rows in front, by window and inside a window by (rank, position) as before,
-// and keeps the tails as they are.  n_off bits + (window bits + 1) bits instead of (n_off + window bits) + (n_off + 1): five 8-bit
-// passes instead of eight at 4.36 M rows and 27 offsets, all on 32-bit keys.
-
-// the rows' Gray ranks, and the identity permutation the sort carries along
-__global__ void k_row_units_ranks(const uint32_t *__restrict__ masks, const int32_t *__restrict__ nbr, int n_off, int64_t nbr_ks,
-                                  int64_t nbr_os, int64_t n, uint32_t *__restrict__ rank, int32_t *__restrict__ iota,
-                                  uint32_t *__restrict__ masks_out) {
-    const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= n) return;
-    uint32_t m = 0;
-    if (masks) {
-        m = masks[o] & (0xffffffffu >> (32 - n_off));
-    } else {
-        for (int k = 0; k < n_off; ++k) m |= (nbr[(int64_t)k * nbr_ks + o * nbr_os] >= 0 ? 1u : 0u) << k;
-        if (masks_out) masks_out[o] = m;
-    }
-    rank[o] = gray_rank(m);
-    iota[o] = (int32_t)o;
-}
-
-// rank[i], row[i]: the rows sorted by rank (stable).  head[i] = i where a run of equal (rank, window) starts, 0 elsewhere: its
-// inclusive maximum scan is every element's run start
-__global__ void k_row_units_heads(const uint32_t *__restrict__ rank, const int32_t *__restrict__ row, int64_t n, int window_log2,
-                                  int32_t *__restrict__ head) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    head[i] = (i > 0 && (rank[i] != rank[i - 1] || (row[i] >> window_log2) != (row[i - 1] >> window_log2))) ? (int32_t)i : 0;
-}
-
-// the last element of every run writes the run's length at the run's start
-__global__ void k_row_units_lengths(const uint32_t *__restrict__ rank, const int32_t *__restrict__ row, const int32_t *__restrict__ start,
-                                    int64_t n, int window_log2, int32_t *__restrict__ len) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (i == n - 1 || rank[i] != rank[i + 1] || (row[i] >> window_log2) != (row[i + 1] >> window_log2))
-        len[start[i]] = (int32_t)(i - start[i] + 1);
-}
-
-// key2 = the window for the rows of a run's whole units, n_windows for its tail
-__global__ void k_row_units_key2(const int32_t *__restrict__ row, const int32_t *__restrict__ start, const int32_t *__restrict__ len,
-                                 int64_t n, int window_log2, int unit, uint32_t n_windows, uint32_t *__restrict__ key2) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int32_t s = start[i];
-    const int32_t whole = len[s] / unit * unit;
-    key2[i] = (int32_t)i - s < whole ? (uint32_t)(row[i] >> window_log2) : n_windows;
-}
-}  // namespace
-}  // namespace fpcc
-
-extern "C" int64_t fpcc_conv_row_order_units(const uint32_t *masks, const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
-                                             int64_t n, int window_log2, int unit, int32_t *order_out, uint32_t *masks_out, void *ws,
-                                             int64_t ws_bytes, void *stream) {
-    if (n < 0 || n > INT32_MAX || n_offsets < 1 || n_offsets > 31 || window_log2 < 5 || window_log2 > 30 || (unit != 32 && unit != 64))
-        return fail_arg("conv_row_order_units: sizes out of range");
-    const size_t nn = (size_t)(n > 0 ? n : 1);
-    const bool one_window = n <= ((int64_t)1 << window_log2);
-    const uint32_t n_windows = (uint32_t)(((int64_t)nn - 1) >> window_log2) + 1;
-    unsigned bits2 = 1;                                          // key2 takes the values 0 .. n_windows
-    while (bits2 < 32 && (n_windows >> bits2)) ++bits2;
-    size_t sort1 = 0, sort2 = 0, scan = 0;
-    FPCC_HIP(rocprim::radix_sort_pairs(nullptr, sort1, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
-                                       (int32_t *)nullptr, nn, 0u, (unsigned)n_offsets));
-    FPCC_HIP(rocprim::radix_sort_pairs(nullptr, sort2, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
-                                       (int32_t *)nullptr, nn, 0u, bits2));
-    FPCC_HIP(rocprim::inclusive_scan(nullptr, scan, (const int32_t *)nullptr, (int32_t *)nullptr, nn, rocprim::maximum<int32_t>()));
-    // workspace: 5 x 32-bit [n] | scratch of the sorts and the scan
-    const int64_t arr = align_up((int64_t)(4 * nn), 256);
-    const int64_t tmp_bytes = align_up((int64_t)std::max(std::max(sort1, sort2), scan), 256);
-    const int64_t need = 5 * arr + tmp_bytes;
-    if (!ws) return need;
-    if (ws_bytes < need) {
-        set_error("conv_row_order_units: workspace %lld < %lld", (long long)ws_bytes, (long long)need);
-        return FPCC_E_WORKSPACE;
-    }
-    if (n == 0) return FPCC_OK;
-    if ((!masks && !nbr) || !order_out) return fail_arg("conv_row_order_units: null pointer");
-    char *p = static_cast<char *>(ws);
-    uint32_t *rank_in = reinterpret_cast<uint32_t *>(p), *rank = reinterpret_cast<uint32_t *>(p + arr);
-    int32_t *iota = reinterpret_cast<int32_t *>(p + 2 * arr), *row = reinterpret_cast<int32_t *>(p + 3 * arr);
-    uint32_t *key2 = reinterpret_cast<uint32_t *>(p + 4 * arr);
-    void *tmp = p + 5 * arr;
-    hipStream_t s = fpcc::as_stream(stream);
-    const dim3 grid(blocks_for(n, 256)), block(256);
-
-    hipLaunchKernelGGL(k_row_units_ranks, grid, block, 0, s, masks, nbr, n_offsets, nbr_ks, nbr_os, n, rank_in, iota, masks_out);
-    FPCC_LAUNCHED(k_row_units_ranks);
-    if (one_window) row = order_out;                             // one window: the rows by rank are the order
-    FPCC_HIP(rocprim::radix_sort_pairs(tmp, sort1, (const uint32_t *)rank_in, rank, (const int32_t *)iota, row, (size_t)n, 0u,
-                                       (unsigned)n_offsets, s));
-    if (one_window) return FPCC_OK;
-
-    // the unsorted ranks and the identity are spent: their space holds the run lengths, the run starts and then the sorted key2
-    int32_t *len = reinterpret_cast<int32_t *>(rank_in), *start = iota, *head = reinterpret_cast<int32_t *>(key2);
-    hipLaunchKernelGGL(k_row_units_heads, grid, block, 0, s, (const uint32_t *)rank, (const int32_t *)row, n, window_log2, head);
-    FPCC_LAUNCHED(k_row_units_heads);
-    FPCC_HIP(rocprim::inclusive_scan(tmp, scan, (const int32_t *)head, start, (size_t)n, rocprim::maximum<int32_t>(), s));
-    hipLaunchKernelGGL(k_row_units_lengths, grid, block, 0, s, (const uint32_t *)rank, (const int32_t *)row, (const int32_t *)start, n,
-                       window_log2, len);
-    FPCC_LAUNCHED(k_row_units_lengths);
-    hipLaunchKernelGGL(k_row_units_key2, grid, block, 0, s, (const int32_t *)row, (const int32_t *)start, (const int32_t *)len, n,
-                       window_log2, unit, n_windows, key2);
-    FPCC_LAUNCHED(k_row_units_key2);
-    uint32_t *key2_sorted = reinterpret_cast<uint32_t *>(start);
-    FPCC_HIP(rocprim::radix_sort_pairs(tmp, sort2, (const uint32_t *)key2, key2_sorted, (const int32_t *)row, order_out, (size_t)n, 0u,
-                                       bits2, s));
-    return FPCC_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -535,7 +535,7 @@ KNOB_WAVE_ON, KNOB_WAVE_NBW, KNOB_WAVE_SB, KNOB_WAVE_DBG, KNOB_MFMA_TILE, KNOB_P
 KNOB_GROUPED_FOLD_ROWS = 4       # rows from which grouped (order 3) layers run folded on one wave per unit; 0 = never
 KNOB_GROUPED_OFF, KNOB_GROUPED_NBW, KNOB_WAVE22_ROWS = 7, 8, 9      # 7: experiments only (FPCC_EXPERIMENT=1), changes the summation order
 KNOB_PERSIST = 12     # workgroups per CU of the persistent grouped / folded kernels (0 = off)
-KNOB_FOLD64 = 13      # folded launches on 64 x 64 wave units: 0 = large maps with a row order, 1 = never, 2 = every folded launch
+KNOB_FOLD64 = 13      # folded launches on 64 x 64 wave units (k_conv_wave64<0x6, true>; earlier profile notes call it k_conv_fold64): 0 = large maps with a row order, 1 = never, 2 = every folded launch
 KNOB_K2S2T_SPARSE = 14  # transposed 2x2x2 convolution over the existing children: 0 = from a child-row threshold, 1 = never, 2 = always
 KNOB_NATURAL_MFMA = 15  # shapes of conv_natural_matrix (order 0, C_out = 256): 0 = VALU kernel, 1 = natural-order matrix kernel, 2 = by a row threshold (default)
 KNOB_LDS_ROWS, KNOB_LDS_ROW_BLOCKS = 10, 11  # rows from which order-3 layers take both operands through LDS (0 = never); row blocks per workgroup (2 | 3 | 4)

@@ -247,7 +247,7 @@ long long fpcc_conv_natural_launches(void);
  *   6  rows from which per-point layers (one offset, identity map) run on the persistent kernel that keeps the weights in
  *      registers (FPCC_POINTWISE_MIN_ROWS, default 32768); 0 = never
  *   8  column blocks per workgroup of the grouped evaluation: 0 = by map size, else 1 | 2 (FPCC_GROUPED_NBW)
- *   9  rows from which order-1 multi-offset layers use 64 x 64 wave tiles (FPCC_WAVE22_MIN_ROWS; 0 = never, the default)
+ *   9  rows from which order-1 multi-offset layers use 64 x 64 wave tiles (k_conv_wave64<SB, false>; FPCC_WAVE22_MIN_ROWS; 0 = never, the default)
  *   7  (NOT result-neutral, refused unless FPCC_EXPERIMENT=1) 1 = evaluate grouped shapes in order 1 instead: A/B experiments
  *  10  rows from which order-3 layers with 64 or 128 output channels take BOTH MFMA operands through LDS (k_conv_lds, conv_lds.hip:
  *      LDS-DMA staging, 2-4 row blocks of a workgroup in lockstep; FPCC_LDS_MIN_ROWS; 0 = never).  Same order 3, same bits.
@@ -259,7 +259,7 @@ long long fpcc_conv_natural_launches(void);
  *   4  rows from which the grouped evaluation runs FOLDED -- one wave per unit adds up the four offset groups itself -- instead of on
  *      four waves per unit (FPCC_GROUPED_FOLD_ROWS, default 102400; 0 = never).  Same order 3, same bits.
  *  13  unit of the folded launches of 27-offset and 8-offset layers with 64 | 128 output channels (FPCC_CONV_FOLD64): 0 = 64 x 64 wave units
- *      (k_conv_fold64) on maps with a row order of at least 204800 rows, 32-row units elsewhere; 1 = 32-row units always; 2 = 64 x 64
+ *      (k_conv_wave64<0x6, true>; earlier profile notes call it k_conv_fold64) on maps with a row order of at least 204800 rows, 32-row units elsewhere; 1 = 32-row units always; 2 = 64 x 64
  *      units on every such launch.  The persistent form (knob 12) keeps its 32-row units.  Same order 3, same bits.
  *  14  transposed 2x2x2 stride-2 convolution onto an existing child map (FPCC_K2S2T_SPARSE), as answered by
  *      fpcc_conv_k2s2t_use_sparse: 0 = over the existing children (fpcc_conv_k2s2t_f32) from 204800 child rows upwards,

@@ -752,6 +752,56 @@ def test_position_ordered_table_on_every_mfma_kernel(ops, scene, c1, c2, c_out, 
     assert torch.equal(by_pos, by_row)
 
 
+@pytest.mark.parametrize('rows', [None, 1, 63, 64, 65, 129])
+@pytest.mark.parametrize('c1,c2,c_out', [(64, 0, 64), (32, 32, 64), (128, 0, 128)])
+def test_plain_64_row_unit_reads_a_position_ordered_table(knobs, scene, request, c1, c2, c_out, rows):
+    """k_conv_wave64<SB, false> (order 1 under knob 7, 64-row units forced by knob 9) shares the prologue of the folded form: beside a
+    row order it reads a row-major table by POSITION.  The offset-major table without (a) and with (b) a row order and the [n][32]
+    table gathered into position order with the same row order (c) give the same bits, and the bits of k_conv_wave (knob 9 = 0), which
+    the oracle tests above pin.  rows: the scene's level, and tables cut to 1 row, 63 / 64 / 65 (an empty second block, the last-row
+    re-read past the end) and 129 (a ragged third unit)."""
+    import os
+    ops = knobs
+    rng = np.random.default_rng(c1 + 5 * c2 + c_out + (rows or 0))
+    table = scene['k3']
+    if rows is not None:
+        table = table[:, :rows].copy()
+        table[table >= rows] = -1
+    n = table.shape[1]
+    x1 = _cuda(rng.normal(size=(n, c1)).astype(np.float32))
+    x2 = _cuda(rng.normal(size=(n, c2)).astype(np.float32)) if c2 else None
+    w = _cuda((rng.normal(size=(27, c1 + c2, c_out)) / np.sqrt(13 * (c1 + c2))).astype(np.float32))
+    b = _cuda(rng.normal(size=c_out).astype(np.float32))
+    slope = torch.tensor([0.2], device='cuda')
+    nbr = _cuda(table)
+    order = ops.conv_row_order(nbr, 27, n, 1, n)
+    rows_pos = ops.transpose_table(nbr, 32).index_select(0, order.long())
+    kw = dict(x2=x2, bias=b, act=ops.ACT_PRELU, slope=slope, pack=True, n_offsets=27)
+    calls = (dict(nbr=nbr, nbr_ks=n, nbr_os=1, row_order=None), dict(nbr=nbr, nbr_ks=n, nbr_os=1, row_order=order),
+             dict(nbr=rows_pos, nbr_ks=1, nbr_os=32, row_order=order))
+    had_env = os.environ.get('FPCC_EXPERIMENT')
+    os.environ['FPCC_EXPERIMENT'] = '1'
+    saved = [(k, ops.conv_set_tuning(k, 1)) for k in (ops.KNOB_GROUPED_OFF, ops.KNOB_WAVE22_ROWS)]
+
+    def restore():
+        for k, v in saved:
+            ops.conv_set_tuning(k, v)
+        if had_env is None:
+            del os.environ['FPCC_EXPERIMENT']
+        else:
+            os.environ['FPCC_EXPERIMENT'] = had_env
+    request.addfinalizer(restore)
+    for sb in (0, 1):
+        ops.conv_set_tuning(ops.KNOB_WAVE_SB, sb)
+        ops.conv_set_tuning(ops.KNOB_WAVE22_ROWS, 0)
+        want = [ops.conv_f32(x1, w, c_out, n, **call, **kw) for call in calls]           # k_conv_wave
+        ops.conv_set_tuning(ops.KNOB_WAVE22_ROWS, 1)
+        got = [ops.conv_f32(x1, w, c_out, n, **call, **kw) for call in calls]
+        for i in range(3):
+            assert torch.equal(got[i].view(torch.int32), got[0].view(torch.int32)), (sb, 'abc'[i])
+            assert torch.equal(got[i].view(torch.int32), want[i].view(torch.int32)), (sb, 'abc'[i], 'against the 32-row units')
+
+
 def test_launch_events_recorded_inside_the_call(ops, scene):
     """fpcc_time_next_launch (hipops.set_thread_trace): the traced launch carries two events recorded inside the C call; their distance
     is the kernel's duration -- positive, and far below the time the host spends between two launches when it sleeps in between"""

@@ -1,4 +1,4 @@
-"""The folded 64 x 64 wave unit (k_conv_fold64; knob KNOB_FOLD64 = 2) against the 32-row folded kernel (KNOB_FOLD64 = 1) and against
+"""The folded 64 x 64 wave unit (k_conv_wave64<0x6, true> -- earlier profile notes call it k_conv_fold64; knob KNOB_FOLD64 = 2) against the 32-row folded kernel (KNOB_FOLD64 = 1) and against
 oracle/sparse_conv.c in summation order 3: all three BIT FOR BIT, so no tolerance is involved.
 
 The new unit folds at the group boundaries of the UNION of its two 32-row blocks' offsets; the tables below are built so that this

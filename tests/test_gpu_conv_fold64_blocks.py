@@ -1,4 +1,4 @@
-"""k_conv_fold64 on units whose two 32-row blocks have different offsets: the forced 64 x 64 unit (KNOB_FOLD64 = 2) against the 32-row
+"""k_conv_wave64<0x6, true> (earlier profile notes call it k_conv_fold64) on units whose two 32-row blocks have different offsets: the forced 64 x 64 unit (KNOB_FOLD64 = 2) against the 32-row
 folded kernel (KNOB_FOLD64 = 1) and oracle/sparse_conv.c in summation order 3, BIT FOR BIT.  These are the tables on which a unit
 that treats its blocks separately (e.g. leaves out the MFMAs of the block that lacks a stage's offset) can go wrong.
 
