@@ -11,7 +11,11 @@ globally best children up to the level's true point count (3 bytes in the header
 Float convolutions and linears run on fpcc_conv_f32 over the hash lookup tables of fastpcc_amd.int_sparse_conv, exactly as
 in the float twin of the LiDAR codec (codecs/lossl_coord): the decoder recomputes the encoder's activations bit for bit
 because every output element is one fixed-order FMA chain.  Softmax -> 16-bit CDF rows are tensor arithmetic as in the
-reference (:501-509) and go to the host coder whole; rANS is the reference's single LIFO stream (rans_coder.py)."""
+reference (:501-509) and go to the host coder whole; rANS is the reference's single LIFO stream (rans_coder.py).
+
+`compress_many` / `decompress_many` code a list of clouds in one traversal, every stream byte for byte the single call's: there the
+rows behind torch's softmax come from fpcc_pmf_to_cdf16_f32 (decoder) or leave the device as the coded symbol's range only
+(fpcc_pmf_to_ranges_f32, encoder), and the lossy levels of all clouds are one fpcc_top_children_batch."""
 import io
 import math
 import time
@@ -34,6 +38,36 @@ from .model_config import Config
 
 log2_e = math.log2(math.e)
 LATENT_BOUND = 20.0          # latents are clipped to [-20, 20] in training (:28-40): 41 values at most reach the coder
+MANY_MAX_CLOUDS = 64         # clouds per traversal of compress_many / decompress_many
+MAX_HOST_THREADS = 16        # host threads that code the clouds of a batch side by side
+
+_HOST_THREADS = None
+_HOST_THREADS_LOCK = __import__('threading').Lock()
+
+
+def _thread_pool():
+    """one pool per process: the jobs (a cloud's rANS stream) are short and independent"""
+    global _HOST_THREADS
+    from concurrent.futures import ThreadPoolExecutor
+    with _HOST_THREADS_LOCK:
+        if _HOST_THREADS is None:
+            _HOST_THREADS = ThreadPoolExecutor(max_workers=MAX_HOST_THREADS, thread_name_prefix='fpcc-v3-coder')
+        return _HOST_THREADS
+
+
+def group_clouds(sizes: List[int], max_voxels: int, max_clouds: int = MANY_MAX_CLOUDS) -> List[List[int]]:
+    """consecutive runs of cloud indices, each run at most max_clouds clouds and -- unless it is one cloud -- max_voxels voxels in all:
+    the clouds one traversal takes"""
+    groups, cur, acc = [], [], 0
+    for i, n in enumerate(sizes):
+        if cur and (acc + n > max_voxels or len(cur) == max_clouds):
+            groups.append(cur)
+            cur, acc = [], 0
+        cur.append(i)
+        acc += n
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 class EntropyModel(nn.Module):
@@ -205,8 +239,9 @@ class OneScalePredictor(nn.Module):
         return cur_rec, rounded, cur_pred, cur_oct
 
     def decompress(self, cur_rec: SparseTensor, cached_points_num: List[int], bin2oct_kernel, unfold_kernel,
-                   rans_decode_fea, rans_decode_oct, if_upsample):
-        """-> features of the next level, or the reconstructed [m, 3] coordinates after the last one (:204-245)"""
+                   rans_decode_fea, rans_decode_oct, if_upsample, lossy_mask=None):
+        """-> features of the next level, or the reconstructed [m, 3] coordinates after the last one (:204-245).
+        lossy_mask (Model.decompress_many): callable(logits) -> the `top_children` mask of a level that holds several clouds"""
         cur_rec = self._trunk(cur_rec)
         for _, _, widen, dec, _ in self.transforms:
             latent = SparseTensor(rans_decode_fea(cur_rec.C.shape[0] * self.compressed_channels, cur_rec.F.device)
@@ -216,8 +251,10 @@ class OneScalePredictor(nn.Module):
         cur_pred = self.pred(cur_rec).F
         if self.if_pred_oct_lossl:
             cur_bin = _bits_of(rans_decode_oct(cur_pred), bin2oct_kernel)
-        else:
+        elif lossy_mask is None:
             cur_bin = top_children(cur_pred, cached_points_num.pop())
+        else:
+            cur_bin = lossy_mask(cur_pred)
         children = _children_of(cur_rec.C, unfold_kernel, cur_bin)
         if if_upsample:
             return self._expand(cur_rec, cur_bin, children)
@@ -267,7 +304,8 @@ class Model(nn.Module):
         self.fea_side_info_cdf2[:, -1] = 65535
         self.rans_encoder = RansEncoder(32 * 1024 * 1024)
         self.rans_decoder = RansDecoder()
-        self.trace: Optional[dict] = None          # tests set a dict: per level logits / latents / symbols of compress()
+        self._extra_encoders: List[RansEncoder] = []       # compress_many: one stream per cloud
+        self.trace: Optional[dict] = None         # tests set a dict: per level logits / latents / symbols of compress()
 
     # ---------------------------------------------------------------------------------------------------------------
     def forward(self, pc_data: PCData):
@@ -366,35 +404,42 @@ class Model(nn.Module):
         symbols._fpcc_children = int_model._children_count(out)
         return symbols
 
-    def rans_encode_fea(self, quantized_cdf: np.ndarray, rounded: np.ndarray, rounded_min: Optional[int] = None):
+    def rans_encode_fea(self, quantized_cdf: np.ndarray, rounded: np.ndarray, rounded_min: Optional[int] = None,
+                        encoder: Optional[RansEncoder] = None):
         """symbols under one shared CDF, then the CDF itself (entries - 1 under a flat 16-bit model), its length and the
         value offset (flat 7-bit model): the decoder pops them in the opposite order"""
-        self.rans_encoder.encode(quantized_cdf[None], rounded)
-        self.rans_encoder.encode(self.fea_side_info_cdf1, quantized_cdf[:-1] - 1)
+        enc = encoder or self.rans_encoder
+        enc.encode(quantized_cdf[None], rounded)
+        enc.encode(self.fea_side_info_cdf1, quantized_cdf[:-1] - 1)
         if len(quantized_cdf) - 2 > self.fea_side_info_cdf2.shape[1] - 1:
             raise ValueError(f'alphabet of {len(quantized_cdf)} values does not fit the side information')
-        self.rans_encoder.encode(self.fea_side_info_cdf2, np.array((len(quantized_cdf) - 2,), dtype=np.uint16))
+        enc.encode(self.fea_side_info_cdf2, np.array((len(quantized_cdf) - 2,), dtype=np.uint16))
         if rounded_min is not None:
             if not 0 <= rounded_min < self.fea_side_info_cdf2.shape[1]:
                 raise ValueError(f'latent offset {rounded_min} does not fit the side information')
-            self.rans_encoder.encode(self.fea_side_info_cdf2, np.array((rounded_min,), dtype=np.uint16))
+            enc.encode(self.fea_side_info_cdf2, np.array((rounded_min,), dtype=np.uint16))
 
-    def rans_decode_fea(self, length: int, device=None, decode_rounded_min: bool = True):
-        """-> float tensor on `device` (latents, offset removed) or, with decode_rounded_min False, the raw uint16 array"""
+    def rans_decode_fea(self, length: int, device=None, decode_rounded_min: bool = True, decoder: Optional[RansDecoder] = None):
+        """-> float tensor on `device` (latents, offset removed; with a `decoder` of its own: the float32 host array) or, with
+        decode_rounded_min False, the raw uint16 array"""
+        dec = decoder or self.rans_decoder
         rounded_min = np.zeros(1, dtype=np.uint16)
         if decode_rounded_min:
-            self.rans_decoder.decode(self.fea_side_info_cdf2, rounded_min)
+            dec.decode(self.fea_side_info_cdf2, rounded_min)
         cdf_len = np.empty(1, dtype=np.uint16)
-        self.rans_decoder.decode(self.fea_side_info_cdf2, cdf_len)
+        dec.decode(self.fea_side_info_cdf2, cdf_len)
         cdf = np.empty(int(cdf_len[0]) + 1, dtype=np.uint16)
-        self.rans_decoder.decode(self.fea_side_info_cdf1, cdf)
+        dec.decode(self.fea_side_info_cdf1, cdf)
         cdf = np.pad(cdf + 1, (0, 1))
         cdf[-1] = 65535
         decoded = np.empty(length, dtype=np.uint16)
-        self.rans_decoder.decode(cdf[None], decoded)
+        dec.decode(cdf[None], decoded)
         if not decode_rounded_min:
             return decoded
-        return torch.from_numpy(decoded.astype(np.float32) - np.float32(rounded_min[0])).to(device)
+        values = decoded.astype(np.float32) - np.float32(rounded_min[0])
+        if decoder is not None:
+            return values                              # one cloud of decompress_many, which joins the clouds before the one copy
+        return torch.from_numpy(values).to(device)
 
     # -- codec (:547-681) ------------------------------------------------------------------------------------------------
     def _block(self, idx: int, blocks) -> OneScalePredictor:
@@ -466,9 +511,231 @@ class Model(nn.Module):
             bs.write(self.rans_encoder.flush())
             return bs.getvalue()
 
+    # -- several clouds in one traversal ---------------------------------------------------------------------------------
+    MANY_MAX_VOXELS = 2_000_000
+
+    def _groups(self, sizes: List[int]) -> List[List[int]]:
+        return group_clouds(sizes, self.MANY_MAX_VOXELS, MANY_MAX_CLOUDS)
+
+    def _cloud_cdfs(self, values: torch.Tensor, cloud_of: torch.Tensor, lengths: List[int], counts: List[int]) -> List[torch.Tensor]:
+        """`histogram_cdf` of every cloud's share of `values` (non-negative integers [n], cloud_of int64 [n]; cloud b holds counts[b]
+        of them, all below lengths[b] >= 2) as int32 device rows: one joint histogram, then per cloud the very operators
+        histogram_cdf applies to that cloud alone (the same counts through the same division and quantisation: the same numbers)"""
+        width = max(lengths)
+        hist = torch.bincount(cloud_of * width + values.long(), minlength=len(lengths) * width).reshape(len(lengths), width)
+        return [self.batch_quantize_pmf_torch((hist[b, :lengths[b]] / counts[b])[None], False)[0] for b in range(len(lengths))]
+
+    @torch.no_grad()
+    def compress_many(self, clouds: List[torch.Tensor]) -> List[bytes]:
+        """B independent clouds (each int32 [n, 4], batch column 0) -> the stream `compress` writes for each, from ONE traversal of
+        the networks: the clouds become the samples of one batch (the hash-table kernel maps key on the batch column, so rows of
+        different clouds never neighbour, and fpcc_conv_f32 sums an output element in an order that depends on the layer's shape alone:
+        a cloud's activations are the bits of its own traversal).  Per coded level one softmax and one fpcc_pmf_to_ranges_f32 launch over
+        all clouds -- 4 bytes per symbol leave the device instead of a 255-entry row -- and each cloud's ranges, latents and bottom
+        coordinates go to its own rANS stream, the clouds' streams coded side by side on host threads.  The header, the latents'
+        offsets and their histogram CDFs are each cloud's own."""
+        B = len(clouds)
+        if B == 0 or not all(c.is_cuda for c in clouds):
+            raise RuntimeError('compress_many() takes a non-empty list of GPU tensors')
+        if B == 1:
+            return [self.compress(clouds[0])]
+        groups = self._groups([c.shape[0] for c in clouds])
+        if len(groups) > 1:
+            return [s for g in groups for s in self.compress_many([clouds[i] for i in g])]
+        device = clouds[0].device
+        offsets = torch.stack([c[:, 1:].amin(0) for c in clouds])                                # [B, 3]
+        parts = []
+        for b, c in enumerate(clouds):                                                           # cloud b = sample b
+            part = c - F.pad(offsets[b], (1, 0))
+            part[:, 0] = b
+            parts.append(part)
+        xyz = torch.cat(parts)
+        keys = ops.morton3d_encode(xyz[:, 1:], (2, 1, 0)) | (xyz[:, 0].to(torch.int64) << 48)   # 'zyx' Morton inside a cloud
+        _, perm = ops.sort_keys(keys)
+        xyz = xyz[perm.long()].contiguous()
+        org = self.get_init_pc(xyz, 1)
+        skip = self.cfg.skip_top_scales_num
+        blocks_enc, blocks_dec = self.blocks_enc[skip:], self.blocks_dec[skip:]
+        levels = self.max_downsample_times - skip
+        if skip and len(self.blocks_enc):
+            raise NotImplementedError('skip_top_scales_num with latent levels: the encoder stack starts at the fold of stride 1')
+        bins = [org]
+        for _ in range(levels):
+            bins.append(self.get_bin(bins[-1]))
+        strided = [org, bins[1]] if len(blocks_enc) else [org]
+        for block in blocks_enc[1:]:
+            strided.append(block(strided[-1]))
+        strided += bins[len(strided):]
+
+        # rows of every cloud on every level (the rows are cloud-major) and the largest bottom coordinate of every cloud: one read-back
+        marks = torch.arange(B + 1, device=device, dtype=torch.int32)
+        top = strided[-1]
+        cloud_of_top = top.C[:, 0].long()
+        bottom_max = torch.zeros(B, dtype=torch.int32, device=device).scatter_reduce_(0, cloud_of_top, top.C[:, 1:].amax(1), 'amax')
+        facts = torch.stack([torch.searchsorted(s.C[:, 0].contiguous(), marks).to(torch.int32) for s in strided]
+                            + [F.pad(bottom_max, (0, 1))]).tolist()
+        edges, bottom_max = facts[:-1], facts[-1][:B]                                            # edges[level][b]: first row of cloud b
+        rows = [[e[b + 1] - e[b] for b in range(B)] for e in edges]
+        if min(rows[0]) < 1:
+            raise ValueError('every cloud needs at least one point')
+        lossy_levels = next((i for i, v in enumerate(self.cfg.lossl_geo_upsample) if v == 1), len(self.cfg.lossl_geo_upsample))
+
+        cur_rec = SparseTensor(org.F[:top.C.shape[0]], top.C, (2 ** levels,) * 3)
+        cur_rec._caches = org._caches
+        stash, stashed = [], 0            # int32 device pieces of the one copy to the host; a piece is named by (offset, length)
+
+        def put(t: torch.Tensor) -> Tuple[int, int]:
+            nonlocal stashed
+            stash.append(t.reshape(-1).to(torch.int32))
+            stashed += t.numel()
+            return stashed - t.numel(), t.numel()
+        coded = []                        # per coded level, coarse to fine: (level, device (start, freq - 1), latents)
+        for idx in range(levels, 0, -1):
+            block = self._block(idx, blocks_dec)
+            cur_rec, rounded, logits, symbols = block.compress(cur_rec, strided[idx], strided[idx - 1], bins[idx].F,
+                                                               self.bin2oct_kernel, if_upsample=idx != 1)
+            if logits is None:
+                break
+            ranges = ops.pmf_to_ranges(F.softmax(logits.float(), dim=-1).contiguous(), symbols.to(torch.int16).contiguous())
+            latents = []
+            if rounded:
+                cloud_of = strided[idx].C[:, 0].long()
+                ends = torch.stack([torch.stack([
+                    torch.full((B,), math.inf, device=device).scatter_reduce_(0, cloud_of, f.amin(1), 'amin'),
+                    torch.full((B,), -math.inf, device=device).scatter_reduce_(0, cloud_of, f.amax(1), 'amax')]) for f in rounded]).tolist()
+                for f, (lo, hi) in zip(rounded, ends):                  # the level's per-cloud extrema came back together
+                    shift = [int(-v) for v in lo]
+                    lengths = [max(int(h) + s + 1, 2) for h, s in zip(hi, shift)]
+                    shifted = (f + torch.tensor(shift, dtype=torch.float32, device=device)[cloud_of][:, None]).to(torch.int32)
+                    cdfs = self._cloud_cdfs(shifted.reshape(-1), cloud_of.repeat_interleave(f.shape[1]), lengths,
+                                            [r * f.shape[1] for r in rows[idx]])
+                    latents.append(([put(c) for c in cdfs], put(shifted), f.shape[1], shift))
+            coded.append((idx, ranges, latents))
+        bottom_lengths = [max(v + 1, 2) for v in bottom_max]
+        bottom_cdfs = [put(c) for c in self._cloud_cdfs(top.C[:, 1:].reshape(-1), cloud_of_top.repeat_interleave(3), bottom_lengths,
+                                                         [3 * r for r in rows[levels]])]
+        bottom_at, _ = put(top.C[:, 1:])
+        offsets_at, _ = put(offsets)
+
+        host_i32 = torch.empty(stashed, dtype=torch.int32, pin_memory=True)
+        host_i32.copy_(torch.cat(stash), non_blocking=True)
+        n_sym = sum(s.shape[0] for _, (s, _), _ in coded)
+        host_i16 = torch.empty(2 * n_sym, dtype=torch.int16, pin_memory=True)
+        if n_sym:
+            host_i16.copy_(torch.cat([s for _, (s, _), _ in coded] + [f for _, (_, f), _ in coded]), non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        ints, pairs = host_i32.numpy(), host_i16.numpy().view(np.uint16)
+        level_at = np.concatenate(([0], np.cumsum([s.shape[0] for _, (s, _), _ in coded]))).tolist()
+        while len(self._extra_encoders) < B - 1:
+            self._extra_encoders.append(RansEncoder(32 * 1024 * 1024))
+        encoders = [self.rans_encoder, *self._extra_encoders[:B - 1]]
+
+        def u16(at: int, n: int) -> np.ndarray:
+            return ints[at: at + n].astype(np.uint16)
+
+        def code_cloud(c: int) -> bytes:
+            enc = encoders[c]
+            for lvl in range(len(coded) - 1, -1, -1):                   # finest level first: the decoder pops coarse -> fine
+                idx, _, latents = coded[lvl]
+                a = level_at[lvl] + edges[idx][c]
+                enc.encode_ranges(pairs[a: a + rows[idx][c]], pairs[n_sym + a: n_sym + a + rows[idx][c]])
+                for cdfs, (sym_at, _), width, shift in reversed(latents):
+                    self.rans_encode_fea(u16(*cdfs[c]), u16(sym_at + edges[idx][c] * width, rows[idx][c] * width), shift[c], encoder=enc)
+            self.rans_encode_fea(u16(*bottom_cdfs[c]), u16(bottom_at + 3 * edges[levels][c], 3 * rows[levels][c]), encoder=enc)
+            head = b''.join(int(v).to_bytes(2, 'little') for v in ints[offsets_at + 3 * c: offsets_at + 3 * c + 3].tolist())
+            head += rows[levels][c].to_bytes(2, 'little')
+            head += b''.join(rows[i][c].to_bytes(3, 'little') for i in range(lossy_levels))
+            return head + enc.flush()
+        jobs = [_thread_pool().submit(code_cloud, c) for c in range(B)]
+        failed = [j.exception() for j in jobs if j.exception() is not None]      # (waits for every job)
+        if failed:
+            for enc in encoders:                                         # a cloud the format cannot carry: leave no coder half full
+                enc.flush()
+            raise failed[0]
+        return [j.result() for j in jobs]
+
+    @torch.no_grad()
+    def decompress_many(self, streams: List[bytes]) -> List[torch.Tensor]:
+        """inverse of compress_many: the clouds' streams decoded in one traversal -- per lossless level one fpcc_pmf_to_cdf16_f32 launch
+        and one copy of uint16 rows (510 B per row) for all clouds, the clouds' symbols and latents decoded side by side on host
+        threads; per lossy level one fpcc_top_children_batch with each stream's own point count.  -> one int32 [n_b, 3] tensor per
+        cloud, what `decompress` returns for its stream"""
+        B = len(streams)
+        if B == 0:
+            raise RuntimeError('decompress_many() takes a non-empty list of streams')
+        if B == 1:
+            return [self.decompress(streams[0])]
+        groups = self._groups([len(s) for s in streams])                 # (bytes ~ voxels at a few bits per voxel: a size proxy)
+        if len(groups) > 1:
+            return [t for g in groups for t in self.decompress_many([streams[i] for i in g])]
+        device = self.fold2bin_kernel.device
+        skip = self.cfg.skip_top_scales_num
+        blocks_dec = self.blocks_dec[skip:]
+        levels = self.max_downsample_times - skip
+        threads = _thread_pool()
+        decoders, offsets, targets, bottoms = [], [], [], []
+        for b, data in enumerate(streams):
+            offsets.append([int.from_bytes(data[i:i + 2], 'little') for i in (0, 2, 4)])
+            n_bottom = int.from_bytes(data[6:8], 'little')
+            pos, mine = 8, []
+            for v in self.cfg.lossl_geo_upsample:
+                if v == 1:
+                    break
+                mine.append(int.from_bytes(data[pos:pos + 3], 'little'))
+                pos += 3
+            targets.append(mine)
+            dec = RansDecoder()
+            dec.flush(data[pos:])
+            bottom = self.rans_decode_fea(n_bottom * 3, decode_rounded_min=False, decoder=dec).astype(np.int32).reshape(-1, 3)
+            bottoms.append(F.pad(torch.from_numpy(bottom), (1, 0, 0, 0), value=b))
+            decoders.append(dec)
+        rows = [b.shape[0] for b in bottoms]                              # rows of every cloud on the level being decoded
+
+        def starts() -> List[int]:
+            return np.concatenate(([0], np.cumsum(rows))).tolist()
+
+        def decode_fea(length: int, dev) -> torch.Tensor:
+            width = length // sum(rows)
+            parts = list(threads.map(lambda c: self.rans_decode_fea(rows[c] * width, decoder=decoders[c]), range(B)))
+            return torch.from_numpy(np.concatenate(parts)).to(dev)
+
+        def decode_oct(logits: torch.Tensor) -> torch.Tensor:
+            rows_d = ops.pmf_to_cdf16(F.softmax(logits.float(), dim=-1).contiguous())
+            if rows_d.shape[0] != sum(rows):
+                raise RuntimeError('the level does not hold the rows the clouds\' streams account for')
+            rows_h = torch.empty(rows_d.shape, dtype=torch.int16, pin_memory=True)
+            rows_h.copy_(rows_d, non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            cdf, out, at = rows_h.numpy().view(np.uint16), np.empty(rows_d.shape[0], dtype=np.uint16), starts()
+
+            def decode_cloud(c: int) -> int:
+                decoders[c].decode(cdf[at[c]: at[c + 1]], out[at[c]: at[c + 1]])
+                return int_model._children_count(out[at[c]: at[c + 1]])
+            rows[:] = threads.map(decode_cloud, range(B))
+            symbols = torch.from_numpy(out.astype(np.int16)).to(logits.device)
+            symbols._fpcc_children = sum(rows)
+            return symbols
+
+        def lossy_mask(logits: torch.Tensor) -> torch.Tensor:
+            at = starts()
+            mask = ops.top_children_batch(logits.contiguous(), at, [t.pop() for t in targets])
+            kept = mask.sum(1, dtype=torch.int64).cumsum(0)[torch.tensor(at[1:], device=mask.device) - 1].tolist()
+            rows[:] = [b - a for a, b in zip([0] + kept[:-1], kept)]
+            mask._fpcc_children = kept[-1]
+            return mask
+
+        cur_rec = self.get_init_pc(torch.cat(bottoms).to(device), 2 ** levels)
+        for idx in range(levels, 0, -1):
+            cur_rec = self._block(idx, blocks_dec).decompress(cur_rec, None, self.bin2oct_kernel, self.unfold_kernel, decode_fea,
+                                                             decode_oct, if_upsample=idx != 1, lossy_mask=lossy_mask)
+        if sum(rows) != cur_rec.shape[0]:
+            raise RuntimeError('decoded point counts do not add up')
+        offset_t = torch.tensor(offsets, device=device, dtype=torch.int32)
+        return [part + offset_t[b][None] for b, part in enumerate(torch.split(cur_rec, rows))]
+
     def compress_partitions(self, batched_coord: List[torch.Tensor]) -> bytes:
-        parts = [self.compress(p) for p in batched_coord[1:]]            # [0] holds the unpartitioned cloud
-        return b''.join(len(s).to_bytes(3, 'little') + s for s in parts)
+        parts = list(batched_coord[1:])                                  # [0] holds the unpartitioned cloud
+        return b''.join(len(s).to_bytes(3, 'little') + s for s in (self.compress_many(parts) if parts else []))
 
     @torch.no_grad()
     def decompress(self, compressed_bytes: bytes) -> torch.Tensor:
@@ -496,12 +763,12 @@ class Model(nn.Module):
         return cur_rec + torch.tensor(coord_offset, device=device, dtype=torch.int32)[None]
 
     def decompress_partitions(self, concat_bytes: bytes) -> torch.Tensor:
-        out, pos = [], 0
+        streams, pos = [], 0
         while pos != len(concat_bytes):
             length = int.from_bytes(concat_bytes[pos:pos + 3], 'little')
-            out.append(self.decompress(concat_bytes[pos + 3: pos + 3 + length]))
+            streams.append(concat_bytes[pos + 3: pos + 3 + length])
             pos += 3 + length
-        return torch.cat(out, 0)
+        return torch.cat(self.decompress_many(streams), 0)
 
     def test_forward(self, pc_data: PCData) -> dict:
         whole = isinstance(pc_data.xyz, torch.Tensor)

@@ -92,7 +92,8 @@ constexpr int kSelBins = 2048;
 // the counting loop of a pass, shared by the single and the batch kernel: workgroup blockIdx.x of gridDim.x strides over the groups
 // [p0, p1) and counts, in its LDS bins, the keys whose higher bits equal `prefix`.  A candidate that is its cell's maximum ranks as +inf.
 // PASS 0: bits 31..21, PASS 1: bits 20..10 under an 11-bit prefix, PASS 2: bits 9..0 under a 22-bit prefix
-template <int PASS, bool SEG>
+// ALL (fpcc_top_children_batch): every candidate ranks with its own value, maxima included
+template <int PASS, bool SEG, bool ALL = false>
 __device__ __forceinline__ void select_count(unsigned *s_h, const float4 *__restrict__ logit, int64_t p0, int64_t p1,
                                              const int32_t *__restrict__ seg, const unsigned *__restrict__ seg_max, unsigned prefix) {
     constexpr int kShift = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
@@ -103,7 +104,7 @@ __device__ __forceinline__ void select_count(unsigned *s_h, const float4 *__rest
         const float v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const unsigned key = f2ord(v[k] == mx ? __builtin_huge_valf() : v[k]);
+            const unsigned key = f2ord(!ALL && v[k] == mx ? __builtin_huge_valf() : v[k]);
             if (PASS == 0 || (key >> (kShift + (PASS == 2 ? 10 : 11))) == prefix) atomicAdd(&s_h[(key >> kShift) & kMask], 1u);
         }
     }
@@ -236,7 +237,7 @@ __device__ __forceinline__ unsigned long long first_rank(int64_t groups, int64_t
 
 // grid = (workgroups per segment, n_seg): workgroup x of segment y strides over that segment's groups.  As in k_select_hist the bins are
 // private to the workgroup in LDS and merged once, one atomic per non-empty bin and workgroup, into the segment's global bins.
-template <int PASS, bool SEG>
+template <int PASS, bool SEG, bool ALL = false>
 __global__ __launch_bounds__(256) void k_select_hist_batch(const float4 *__restrict__ logit, int64_t m, const int64_t *__restrict__ edges,
                                                            const int64_t *__restrict__ targets, const int32_t *__restrict__ seg,
                                                            const unsigned *__restrict__ seg_max, const SelectState *__restrict__ st,
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(256) void k_select_hist_batch(const float4 *__restr
     const unsigned prefix = PASS ? st[s].prefix : 0u;
     for (int i = threadIdx.x; i < kSelBins; i += 256) s_h[i] = 0;
     __syncthreads();
-    select_count<PASS, SEG>(s_h, logit, p0, p1, seg, seg_max, prefix);
+    select_count<PASS, SEG, ALL>(s_h, logit, p0, p1, seg, seg_max, prefix);
     __syncthreads();
     unsigned *mine = hist + (size_t)s * kSelBins;
     for (int i = threadIdx.x; i < kSelBins; i += 256)
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(256) void k_keep_thr_batch(const float4 *__restrict
 
 int64_t select_batch_ws_bytes(int n_seg) { return align_up((int64_t)sizeof(SelectState) * n_seg, 256) + (int64_t)4 * kSelBins * n_seg; }
 
-template <bool SEG>
+template <bool SEG, bool ALL = false>
 int select_and_keep_batch(const float *logit, int64_t m, const int64_t *edges, int n_seg, const int64_t *targets, const int32_t *seg,
                           const unsigned *seg_max, uint8_t *keep_out, void *ws, hipStream_t s) {
     SelectState *st = static_cast<SelectState *>(ws);
@@ -313,15 +314,85 @@ int select_and_keep_batch(const float *logit, int64_t m, const int64_t *edges, i
     // on a few hot bins); a segment that is larger than its share strides, one that is smaller leaves early
     const unsigned per_seg = (unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks_for(m, 256), 256 / n_seg));
     const dim3 grid(per_seg, (unsigned)n_seg);
-    hipLaunchKernelGGL((k_select_hist_batch<0, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL((k_select_hist_batch<0, SEG, ALL>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
     hipLaunchKernelGGL(k_select_pick_batch<0>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
-    hipLaunchKernelGGL((k_select_hist_batch<1, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL((k_select_hist_batch<1, SEG, ALL>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
     hipLaunchKernelGGL(k_select_pick_batch<1>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
-    hipLaunchKernelGGL((k_select_hist_batch<2, SEG>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
+    hipLaunchKernelGGL((k_select_hist_batch<2, SEG, ALL>), grid, dim3(256), 0, s, lg, m, edges, targets, seg, seg_max, (const SelectState *)st, hist);
     hipLaunchKernelGGL(k_select_pick_batch<2>, dim3(n_seg), dim3(256), 0, s, hist, st, edges, targets);
     hipLaunchKernelGGL(k_keep_thr_batch<SEG>, dim3(blocks_for(m, kThreads)), dim3(kThreads), 0, s, lg, m, edges, n_seg, seg, seg_max,
                        (const SelectState *)st, keep_out);
     return check_hip(hipGetLastError(), "topk select (batch)");
+}
+
+// ---- fp32 probabilities -> 16-bit CDF rows (the float octree codecs: torch's softmax stays the definition of the stream) ---------------
+// One wave per row, rows of up to 256 entries, lane l owns the columns 4l .. 4l+3.  q = floorf(p * (65536 - c)) + 1 is an integer of at
+// most 17 bits and a row's sum stays below 2^24, so the int32 prefix sum below is the float cumsum of the tensor formulation, entry for
+// entry.  Rows start at any multiple of 4 bytes (255 columns: 1020 B in, 510 B out): scalar loads and stores.
+// MODE 1: uint16 CDF rows; MODE 2: (start, freq - 1) of one symbol per row.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pmf_rows(const float *__restrict__ p, int64_t n, int c, uint16_t *__restrict__ cdf_out,
+                                                  const int16_t *__restrict__ sym, int16_t *__restrict__ start_out,
+                                                  int16_t *__restrict__ freqm1_out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;                                                       // (uniform over the wave)
+    const float *x = p + row * c;
+    const float scale = (float)(65536 - c);
+    int32_t f[4];
+    int32_t run = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = 4 * lane + j;
+        if (e < c) run += (int32_t)floorf(__fmul_rn(x[e], scale)) + 1;
+        f[j] = run;                                                             // inclusive within the lane
+    }
+    int32_t scan = run;                                                         // inclusive scan of the lane totals
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t up = __shfl_up(scan, o);
+        if (lane >= o) scan += up;
+    }
+    const int32_t before = scan - run;
+    uint16_t edge[4];                                                           // upper edge of entry e, narrowed by wrapping
+#pragma unroll
+    for (int j = 0; j < 4; ++j) edge[j] = 4 * lane + j == c - 1 ? (uint16_t)65535u : (uint16_t)(uint32_t)(before + f[j]);
+    if (MODE == 1) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (4 * lane + j < c) cdf_out[row * c + 4 * lane + j] = edge[j];
+        return;
+    }
+    // MODE 2: the range of symbol s is [edge[s-1], edge[s]) with edge[-1] = 0 and the last upper edge 65536
+    const int s = (int)(uint16_t)sym[row];
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int e = 4 * lane + j;
+        if (e == s - 1) lo = edge[j];
+        if (e == s) hi = e == c - 1 ? 65536u : (uint32_t)edge[j];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {                                          // exactly one lane holds each of the two
+        lo += __shfl_xor(lo, o);
+        hi += __shfl_xor(hi, o);
+    }
+    if (lane == 0) {
+        start_out[row] = (int16_t)(uint16_t)lo;
+        freqm1_out[row] = (int16_t)(uint16_t)(hi - lo - 1u);
+    }
+}
+
+int pmf_rows(int mode, const float *p, int64_t n, int c, uint16_t *cdf, const int16_t *sym, int16_t *start, int16_t *freqm1, void *stream) {
+    if (n < 0 || c < 2 || c > 256) return fail_arg("pmf rows: n >= 0 rows of 2..256 entries");
+    if (n == 0) return FPCC_OK;
+    if (!p) return fail_arg("pmf rows: null pointer");
+    if (n > (int64_t)4 * 0x7fffffff) return fail_arg("pmf rows: too many rows for one launch");
+    const dim3 grid(blocks_for(n, 4)), block(256);
+    if (mode == 1) hipLaunchKernelGGL(k_pmf_rows<1>, grid, block, 0, as_stream(stream), p, n, c, cdf, sym, start, freqm1);
+    else hipLaunchKernelGGL(k_pmf_rows<2>, grid, block, 0, as_stream(stream), p, n, c, cdf, sym, start, freqm1);
+    FPCC_LAUNCHED(k_pmf_rows);
+    return FPCC_OK;
 }
 
 }  // namespace
@@ -415,4 +486,31 @@ extern "C" int64_t fpcc_topk_keep_batch(const float *logit, int64_t m, const int
                        seg_max);
     FPCC_LAUNCHED(k_seg_max);
     return select_and_keep_batch<true>(logit, m, seg_edges, n_seg, targets, cell_of_group, (const unsigned *)seg_max, keep_out, ws, s);
+}
+
+extern "C" int64_t fpcc_top_children_batch(const float *logit, int64_t m, const int64_t *seg_edges, int n_seg, const int64_t *points_num,
+                                           uint8_t *mask_out, void *ws, int64_t ws_bytes, void *stream) {
+    if (m < 0) return fail_arg("top_children_batch: negative size");
+    if (n_seg < 1 || n_seg > kMaxSegments) return fail_arg("top_children_batch: 1 <= n_seg <= 256 (FPCC_TOPK_BATCH_MAX_SEGMENTS)");
+    const int64_t need = select_batch_ws_bytes(n_seg);
+    if (!ws) return need;
+    if (ws_bytes < need) { set_error("top_children_batch: workspace %lld < %lld", (long long)ws_bytes, (long long)need); return FPCC_E_WORKSPACE; }
+    if (m == 0) return FPCC_OK;
+    if (!logit || !mask_out || !seg_edges || !points_num) return fail_arg("top_children_batch: null pointer");
+    if ((reinterpret_cast<uintptr_t>(logit) & 15) || (reinterpret_cast<uintptr_t>(mask_out) & 7) || (reinterpret_cast<uintptr_t>(ws) & 15) ||
+        (reinterpret_cast<uintptr_t>(seg_edges) & 7) || (reinterpret_cast<uintptr_t>(points_num) & 7))
+        return fail_arg("top_children_batch: logit / workspace must be 16-byte, mask_out / seg_edges / points_num 8-byte aligned");
+    // the passes rank every value (ALL); the final mask is the one of fpcc_topk_keep_batch: x > thr or x == its row's maximum
+    return select_and_keep_batch<false, true>(logit, m, seg_edges, n_seg, points_num, nullptr, nullptr, mask_out, ws, as_stream(stream));
+}
+
+extern "C" int fpcc_pmf_to_cdf16_f32(const float *p, int64_t n, int c, uint16_t *cdf_out, void *stream) {
+    if (n > 0 && !cdf_out) return fail_arg("pmf_to_cdf16_f32: null pointer");
+    return pmf_rows(1, p, n, c, cdf_out, nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" int fpcc_pmf_to_ranges_f32(const float *p, int64_t n, int c, const int16_t *symbols, int16_t *start_out,
+                                      int16_t *freq_minus_1_out, void *stream) {
+    if (n > 0 && (!symbols || !start_out || !freq_minus_1_out)) return fail_arg("pmf_to_ranges_f32: null pointer");
+    return pmf_rows(2, p, n, c, nullptr, symbols, start_out, freq_minus_1_out, stream);
 }

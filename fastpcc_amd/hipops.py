@@ -100,6 +100,9 @@ _SIGS = {
     'fpcc_topk_keep': (_i64, [_vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     'fpcc_topk_keep_cells': (_i64, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp]),
     'fpcc_topk_keep_batch': (_i64, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    'fpcc_top_children_batch': (_i64, [_vp, _i64, _vp, _i32, _vp, _vp, _vp, _i64, _vp]),
+    'fpcc_pmf_to_cdf16_f32': (_i32, [_vp, _i64, _i32, _vp, _vp]),
+    'fpcc_pmf_to_ranges_f32': (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     'fpcc_gather_rows_f32': (_i32, [_vp, _i32, _i32, _vp, _i64, _vp, _i32, _vp]),
     'fpcc_compact_coords': (_i64, [_vp, _i64, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_int_init': (_i32, []),
@@ -1499,6 +1502,32 @@ def topk_keep_batch(logit: torch.Tensor, seg_edges: Sequence[int], targets: Sequ
     return out
 
 
+def top_children_batch(logit: torch.Tensor, seg_edges: Sequence[int], points_num: Sequence[int]) -> torch.Tensor:
+    """uint8 [m, 8]: `top_children` of codecs/lossy_coord_v3 for every segment of a batch in ONE set of launches
+    (fpcc_top_children_batch).  logit fp32 [m, 8]; seg_edges: host list [n_seg + 1] of ROW offsets, 0 first and m last; points_num: host
+    list [n_seg].  mask[a:b] of segment [a, b) equals, byte for byte, top_children(logit[a:b], points_num[s]): every row's best child
+    and every child above the (8 rows - points_num)-th smallest VALUE of the segment (all values rank, unlike topk_keep_batch)."""
+    if logit.dim() != 2 or logit.shape[1] != 8:
+        raise ValueError('logits must be [m, 8]')
+    m = logit.shape[0]
+    edges, targets = [int(e) for e in seg_edges], [int(t) for t in points_num]
+    n_seg = len(targets)
+    if not 1 <= n_seg <= TOPK_BATCH_MAX_SEGMENTS:
+        raise ValueError(f'1 to {TOPK_BATCH_MAX_SEGMENTS} segments per call, got {n_seg}')
+    if len(edges) != n_seg + 1 or edges[0] != 0 or edges[-1] != m or any(b < a for a, b in zip(edges[:-1], edges[1:])):
+        raise ValueError('seg_edges must rise from 0 to the number of rows, one more entry than points_num')
+    if any(t < 0 for t in targets):
+        raise ValueError('negative point count')
+    out = torch.empty((m, 8), dtype=torch.uint8, device=logit.device)
+    L = lib()
+    ws, need = _ws(lambda: L.fpcc_top_children_batch(None, m, None, n_seg, None, None, None, 0, None), logit.device)
+    # one small copy for both lists, from pinned memory: the host does not wait for the stream
+    meta = torch.tensor(edges + targets, dtype=torch.int64, pin_memory=True).to(logit.device, non_blocking=True)
+    _ok(L.fpcc_top_children_batch(_dev(logit, torch.float32, 'logit'), m, meta.data_ptr(), n_seg, meta.data_ptr() + 8 * (n_seg + 1),
+                                  out.data_ptr(), ws.data_ptr(), need, _stream()))
+    return out
+
+
 def compact_coords(pkeys: torch.Tensor, mask: torch.Tensor, level: int, bits: int,
                    offset_xyz: Optional[torch.Tensor] = None):
     """Children (of parents pkeys at level+1) selected by mask -> xyz int32 [<=8m, 3] at `level`, + count (device)."""
@@ -1848,6 +1877,27 @@ def logits_to_ranges(logits: torch.Tensor, pre_shift: int, symbols: torch.Tensor
     freqm1 = torch.empty(n, dtype=torch.int16, device=logits.device)
     _ok(lib().fpcc_logits_to_ranges(_dev(logits, torch.int32, 'logits'), n, c, pre_shift,
                                     _dev(symbols, torch.int16, 'symbols'), start.data_ptr(), freqm1.data_ptr(), _stream()))
+    return start, freqm1
+
+
+def pmf_to_cdf16(p: torch.Tensor) -> torch.Tensor:
+    """fp32 probabilities [n, c] (what F.softmax returned) -> uint16 CDF rows in an int16 tensor (same bits): floor(p * (65536 - c)) + 1,
+    cumulative sum, last entry 65535 (fpcc_pmf_to_cdf16_f32)"""
+    n, c = p.shape
+    out = torch.empty((n, c), dtype=torch.int16, device=p.device)
+    _ok(lib().fpcc_pmf_to_cdf16_f32(_dev(p, torch.float32, 'p'), n, c, out.data_ptr(), _stream()))
+    return out
+
+
+def pmf_to_ranges(p: torch.Tensor, symbols: torch.Tensor):
+    """-> (start, freq - 1) int16 [n] (uint16 bits) of symbols[i] under row i of pmf_to_cdf16(p), for RansEncoder.encode_ranges"""
+    n, c = p.shape
+    if symbols.shape != (n,):
+        raise ValueError('one symbol per row expected')
+    start = torch.empty(n, dtype=torch.int16, device=p.device)
+    freqm1 = torch.empty(n, dtype=torch.int16, device=p.device)
+    _ok(lib().fpcc_pmf_to_ranges_f32(_dev(p, torch.float32, 'p'), n, c, _dev(symbols, torch.int16, 'symbols'), start.data_ptr(),
+                                     freqm1.data_ptr(), _stream()))
     return start, freqm1
 
 

@@ -560,6 +560,30 @@ int64_t fpcc_topk_keep_cells(const float *logit, int64_t m, const int32_t *cell_
 int64_t fpcc_topk_keep_batch(const float *logit, int64_t m, const int64_t *seg_edges, int n_seg, const int32_t *cell_of_group,
                              int64_t n_cells, const int64_t *targets, uint8_t *keep_out, void *ws, int64_t ws_bytes, void *stream);
 
+/* top_children of the octree codec with coded latents (models/convolutional/lossy_coord_v3/model.py:216-221) for MANY segments (the
+ * clouds of decompress_many) in one set of launches.  NOT the rule above: the threshold ranks ALL values of the segment, a row's
+ * maximum included (fpcc_topk_keep* rank cell maxima as +inf).  logit [m][8]; segment s holds the ROWS [seg_edges[s], seg_edges[s+1])
+ * (device int64 [n_seg + 1], 0 first, m last, rising; not checked here) and points_num[s] (device int64 [n_seg]) is its target:
+ *     k = 8 rows - points_num[s];  k < 1: every entry 1;  else thr = the k-th smallest (1-based) of the segment's 8 rows values and
+ *     mask = (x == max of x's row) | (x > thr),
+ * compared by float value (-0 == +0; logits are finite).  mask_out uint8 [m][8] equals torch's result on each segment alone, byte for
+ * byte.  The same radix-select passes as fpcc_topk_keep_batch: the segment is the second grid dimension, the bins are [n_seg][2048],
+ * the number of launches does not depend on n_seg, nothing is read back.  1 <= n_seg <= FPCC_TOPK_BATCH_MAX_SEGMENTS, else FPCC_E_ARG.
+ * ws (16-byte aligned): the size the call returns with ws == NULL. */
+int64_t fpcc_top_children_batch(const float *logit, int64_t m, const int64_t *seg_edges, int n_seg, const int64_t *points_num,
+                                uint8_t *mask_out, void *ws, int64_t ws_bytes, void *stream);
+
+/* Float siblings of fpcc_logits_to_cdf16 / fpcc_logits_to_ranges for the codecs whose softmax is torch's: they start AFTER the
+ * softmax.  p [n][c] fp32 probabilities (contiguous rows; no alignment beyond 4 bytes is assumed per row), 2 <= c <= 256.  Per row
+ *     q_j = floorf(p_j * (float)(65536 - c)) + 1      (one fp32 multiplication, not contracted)
+ * then the inclusive prefix sum (integers below 2^24: exact in any order), the last entry 65535, every entry narrowed int32 -> uint16
+ * by wrapping: bit for bit Model.batch_quantize_pmf_torch(p, softmax=False) of codecs/lossy_coord_v3 moved to the host as uint16. */
+int fpcc_pmf_to_cdf16_f32(const float *p, int64_t n, int c, uint16_t *cdf_out, void *stream);
+/* Encoder side of the same: only the (start, freq - 1) of the coded symbol of every row (symbols int16 [n], 0 <= symbol < c), in the
+ * convention of fpcc_logits_to_ranges, ready for fpcc_simple_enc_push_ranges. */
+int fpcc_pmf_to_ranges_f32(const float *p, int64_t n, int c, const int16_t *symbols, int16_t *start_out, int16_t *freq_minus_1_out,
+                           void *stream);
+
 /* Rate term of the noisy deep-factorised bottleneck (training): for y [n][c] (row stride ldy) and the per-channel parameters of a
  * 1-3-3-3-3-1 logit network -- weights[i] [c][f_out][f_in], biases[i] [c][f_out], factors[i] [c][f_out], raw as stored
  * (softplus / tanh applied inside) --
