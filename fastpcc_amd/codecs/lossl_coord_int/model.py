@@ -23,6 +23,7 @@ import torch.nn.functional as F
 
 from ... import hipops as ops
 from ...data import PCData
+from ...evaluators import log_against_raw_points
 from ...int_sparse_conv import LinearIn8W8Out8, LinearIn8W8Out32, LinearPReLUIn8W8Out8, LinearPReLUIn8W8Out32, \
     PReLUIn32Out32, RequantFxpToScaledInt8, ROW_ORDER_MIN_ROWS, ROW_ORDER_WINDOW_LOG2, SharedFxpShift, SparseConvIn8W8Out8, \
     SparseConvIn8W8Out32, SparseConvPReLUIn8W8Out8, SparseConvPReLUIn8W8Out32, SparseResBlockIn32W8Out32, SparseTensor, \
@@ -1019,5 +1020,8 @@ class Model(nn.Module):
             data = pc_data.inv_transform[0].numpy().astype('<f4').tobytes() + data
         n_org = pc_data.org_points_num[0] if pc_data.org_points_num else \
             (pc_data.xyz.shape[0] if whole else pc_data.xyz[0].shape[0])
-        return {'pred': recon, 'compressed_bytes': data, 'bpp': 8 * len(data) / n_org, 'encode time': t1 - t0,
-                'decode time': t2 - t1}
+        ret = {'pred': recon, 'compressed_bytes': data, 'bpp': 8 * len(data) / n_org, 'encode time': t1 - t0,
+               'decode time': t2 - t1}
+        # a sweep in metres that carries its raw points: D1 / D2 against them, logged on self.evaluator (evaluators.py)
+        ret.update(log_against_raw_points(self, pc_data, recon, data, n_org, {'encode time': t1 - t0, 'decode time': t2 - t1}))
+        return ret

@@ -268,9 +268,15 @@ class PCC(nn.Module):
         if pc_data.resolution is not None:
             # the reference hands the reconstruction to PCCEvaluator (model.py:215-228), which runs pc_error on files;
             # here the D1 distortion is computed on the device from the tensors at hand
-            self.evaluator.log(pred=coord_recon, org_points_num=n_org, compressed_bytes=compressed_bytes,
-                               file_path=pc_data.file_path[0] if pc_data.file_path else f'sample{len(self.evaluator.file_path_to_info)}',
-                               resolution=pc_data.resolution[0], results_dir=pc_data.results_dir,
+            file_path = pc_data.file_path[0] if pc_data.file_path else f'sample{len(self.evaluator.file_path_to_info)}'
+            # a sample in metres (inv_transform) is measured against its raw float points where it carries them, as the reference
+            # measures against the sweep's `_n.ply` (lib/evaluators.py:100-108): D1 / D2 of float clouds
+            raw = pc_data.inv_transform is not None and pc_data.org_xyz is not None
+            self.evaluator.log(pred=pred_xyz if raw else coord_recon, org_points_num=n_org, compressed_bytes=compressed_bytes,
+                               file_path=file_path, resolution=pc_data.resolution[0], results_dir=pc_data.results_dir,
                                extra_info_dict={'encode time': t1 - t0, 'decode time': t3 - t2},
-                               org_xyz=org[:, 1:] if pc_data.inv_transform is None else None)
+                               org_xyz=pc_data.org_xyz[0].to(pred_xyz.device) if raw else
+                               (org[:, 1:] if pc_data.inv_transform is None else None))
+            if raw:
+                ret.update({k: v for k, v in self.evaluator.file_path_to_info[file_path].items() if k.endswith(('(p2point)', '(p2plane)'))})
         return ret

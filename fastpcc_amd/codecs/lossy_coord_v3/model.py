@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from ... import hipops as ops
 from ...data import PCData
 from ...entropy_models import _NoisyDeepFactorized, make_parameters
+from ...evaluators import log_against_raw_points
 from ...int_sparse_conv import Conv3d, SparseTensor
 from ...rans_coder import RansDecoder, RansEncoder
 from ..lossl_coord.model import Block, SparseSequential
@@ -784,7 +785,11 @@ class Model(nn.Module):
             inv = pc_data.inv_transform[0].to(recon.device)
             recon = recon * inv[3] + inv[None, :3]
             data = pc_data.inv_transform[0].numpy().astype('<f4').tobytes() + data
-        return {'compressed_bytes': data, 'pred': recon, 'encode time': t1 - t0, 'decode time': t2 - t1}
+        ret = {'compressed_bytes': data, 'pred': recon, 'encode time': t1 - t0, 'decode time': t2 - t1}
+        # a sweep in metres that carries its raw points: D1 / D2 against them, logged on self.evaluator (evaluators.py)
+        n_org = pc_data.org_points_num[0] if pc_data.org_points_num else (pc_data.xyz.shape[0] if whole else pc_data.xyz[0].shape[0])
+        ret.update(log_against_raw_points(self, pc_data, recon, data, n_org, {'encode time': t1 - t0, 'decode time': t2 - t1}))
+        return ret
 
 
 class Fold(nn.Module):

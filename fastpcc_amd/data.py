@@ -34,12 +34,15 @@ class PCData:
     inv_transform: Optional[List[torch.Tensor]] = None
     results_dir: Optional[str] = None
     training_step: Optional[int] = None
+    org_xyz: Optional[List[torch.Tensor]] = None      # test samples: per sample the raw float32 points the distortion is measured against
 
     def to(self, device, non_blocking=False):
         if isinstance(self.xyz, torch.Tensor):
             self.xyz = self.xyz.to(device, non_blocking=non_blocking).contiguous()
         else:
             self.xyz = [t.to(device, non_blocking=non_blocking).contiguous() for t in self.xyz]
+        if self.org_xyz is not None:
+            self.org_xyz = [t.to(device, non_blocking=non_blocking).contiguous() for t in self.org_xyz]
         return self
 
 
@@ -137,14 +140,14 @@ def pc_data_collate_fn(data_list: List[PCData], kd_tree_partition_max_points_num
             if all(getattr(d, name) is not None for d in data_list) else None
         return PCData(xyz=xyz, batch_size=len(data_list), color=torch.cat(colors, 0) if all(c is not None for c in colors) else None,
                       org_points_num=gather('org_points_num') or sizes, resolution=gather('resolution'),
-                      file_path=gather('file_path'), inv_transform=gather('inv_transform'),
+                      file_path=gather('file_path'), inv_transform=gather('inv_transform'), org_xyz=gather('org_xyz'),
                       results_dir=data_list[0].results_dir)
     d = data_list[0]
     parts, (color_parts,) = kd_tree_partition(d.xyz, kd_tree_partition_max_points_num, [d.color])
     pad = lambda t: torch.nn.functional.pad(t.to(torch.int32), (1, 0, 0, 0), value=0)
     out = PCData(xyz=[pad(d.xyz)] + [pad(p) for p in parts], batch_size=1,
                  color=None if d.color is None else [d.color] + color_parts)
-    for name in ('org_points_num', 'resolution', 'file_path', 'inv_transform'):
+    for name in ('org_points_num', 'resolution', 'file_path', 'inv_transform', 'org_xyz'):
         v = getattr(d, name)
         setattr(out, name, None if v is None else (v if isinstance(v, list) else [v]))
     out.results_dir = d.results_dir
@@ -172,12 +175,14 @@ def voxelize_points(xyz, scale: float, device=None):
 
 def kitti_odometry_sample(file_path: str, resolution: float = 4096, device=None) -> PCData:
     """one test sample as KITTIOdometry.__getitem__ builds it for a .bin sweep (400 m range mapped onto `resolution` cells,
-    inv_transform = (origin, metres per cell), peak value 59.70 + 1 for the distortion metric)"""
+    inv_transform = (origin, metres per cell), peak value 59.70 + 1 for the distortion metric, org_xyz = the raw points, which the
+    reference writes to the sweep's `_n.ply` for pc_error, dataset.py:77-83)"""
     raw = read_kitti_bin(file_path)
     scale, inv_scale = (resolution - 1) / 400, 400 / (resolution - 1)
     vox, origin = voxelize_points(raw, scale, device)
     inv = torch.cat([origin.cpu().reshape(-1), torch.tensor([inv_scale], dtype=torch.float32)]).to(torch.float32)
-    return PCData(xyz=vox, file_path=[file_path], org_points_num=[raw.shape[0]], resolution=[59.70 + 1], inv_transform=[inv])
+    return PCData(xyz=vox, file_path=[file_path], org_points_num=[raw.shape[0]], resolution=[59.70 + 1], inv_transform=[inv],
+                  org_xyz=[torch.from_numpy(raw).to(vox.device)])
 
 
 # ---- PLY ----------------------------------------------------------------------------------------------------------------

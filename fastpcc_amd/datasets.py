@@ -192,6 +192,12 @@ class KITTIOdometry(_Base):
         sweep = path.endswith('bin')
         xyz = read_kitti_bin(path) if sweep else np.asarray(read_ply_file(path)[0], dtype=np.float32)
         n_org = xyz.shape[0]
+        org_xyz = None
+        if not self.is_training:
+            # what the distortion is measured against: the points the reference writes to the sweep's `_n.ply` (dataset.py:77-88) --
+            # the raw sweep, or its unique millimetre grid points (`_q1mm_n.ply`); a PLY entry is evaluated against itself
+            raw = np.unique((xyz * 1000).round(), axis=0) if sweep and cfg.flag_sparsepcgc else xyz
+            org_xyz = torch.from_numpy(np.array(raw, dtype=np.float32))
         scale = (cfg.resolution - 1) / 400 if sweep else cfg.ply_file_coord_scaler
         if self.is_training and cfg.random_rotation:
             a = float(torch.rand(1).item()) * 2 * math.pi
@@ -216,7 +222,7 @@ class KITTIOdometry(_Base):
             peak, inv = 30000 + 1, inv * 1000
         else:
             peak = cfg.ply_file_resolution
-        return PCData(xyz=vox, file_path=path, org_points_num=n_org, resolution=peak, inv_transform=inv)
+        return PCData(xyz=vox, file_path=path, org_points_num=n_org, resolution=peak, inv_transform=inv, org_xyz=org_xyz)
 
     def collate_fn(self, batch):
         if not self.is_training:

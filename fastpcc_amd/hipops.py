@@ -70,6 +70,12 @@ _SIGS = {
     'fpcc_transfer_normals_ws_bytes': (_i64, [_i64, _i64]),
     'fpcc_transfer_normals': (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
     'fpcc_sum_max_f64': (_i32, [_vp, _i64, _vp, _vp, _i64, _vp]),
+    'fpcc_point_cell_keys': (_i32, [_vp, _i64, _vp, C.c_double, _i32, _vp, _vp]),
+    'fpcc_knn_points': (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _vp]),
+    'fpcc_nn_points': (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    'fpcc_pca_normals_points': (_i32, [_vp, _i64, _vp, _i64, _i32, _vp, _vp]),
+    'fpcc_transfer_normals_points_ws_bytes': (_i64, [_i64, _i64]),
+    'fpcc_transfer_normals_points': (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_recolor_ws_bytes': (_i64, [_i64]),
     'fpcc_recolor': (_i32, [_vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _i64, _vp]),
     'fpcc_keys_member': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp]),
@@ -1071,6 +1077,99 @@ def sum_max_f64(values: torch.Tensor) -> torch.Tensor:
     out = torch.empty(2, dtype=torch.float64, device=values.device)
     ws = torch.empty(max(2 * ((n + 4095) // 4096), 2), dtype=torch.float64, device=values.device)
     _ok(lib().fpcc_sum_max_f64(_dev(values, torch.float64, 'values', n == 0), n, out.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()))
+    return out
+
+
+# ---- float point clouds (metrics_points.hip) --------------------------------------------------------------------------------------
+class _PointGrid(C.Structure):
+    """fpcc_point_grid"""
+    _fields_ = [('keys', _vp), ('points', _vp), ('index', _vp), ('m', _i64), ('origin', C.c_double * 3), ('inv_h', C.c_double),
+                ('bits', _i32), ('reserved', _i32)]
+
+
+class PointGrid:
+    """A float cloud [m, 3] binned for searching (fpcc_point_grid): cells of edge `h` on a grid of 2^bits cells per axis from `origin`.
+    Keeps the caller's points, the points in key order, the sorted keys and the caller's row of every sorted row.  The grid decides
+    speed only, never a result."""
+
+    def __init__(self, points: torch.Tensor, origin: Sequence[float], h: float, bits: int):
+        if points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError('points must be float32 [m, 3]')
+        if not (1 <= int(bits) <= 21) or not h > 0:
+            raise ValueError('bits must be 1..21 and h positive')
+        self.points = points
+        self.origin, self.h, self.bits = tuple(float(v) for v in origin), float(h), int(bits)
+        m = points.shape[0]
+        keys = torch.empty(m, dtype=torch.int64, device=points.device)
+        org = (C.c_double * 3)(*self.origin)
+        _ok(lib().fpcc_point_cell_keys(_dev(points, torch.float32, 'points', m == 0), m, C.addressof(org), 1.0 / self.h, self.bits,
+                                       keys.data_ptr(), _stream()))
+        if m:
+            self.keys, self.index = sort_keys(keys, 3 * self.bits)
+            self.sorted_points = points[self.index.long()].contiguous()
+        else:
+            self.keys, self.index, self.sorted_points = keys, torch.empty(0, dtype=torch.int32, device=points.device), points
+        self.c = _PointGrid(self.keys.data_ptr() if m else None, self.sorted_points.data_ptr() if m else None,
+                            self.index.data_ptr() if m else None, m, org, 1.0 / self.h, self.bits, 0)
+
+    @property
+    def ptr(self):
+        return C.addressof(self.c)
+
+
+def _points3(t: torch.Tensor, name: str):
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f'{name} must be float32 [n, 3]')
+    return _dev(t, torch.float32, name, t.shape[0] == 0)
+
+
+def knn_points(grid: PointGrid, query: torch.Tensor, k: int):
+    """the k (1..32) nearest points of every float32 query row [n, 3], ordered by (float64 squared distance, row in the caller's array):
+    (rows int32 [n, k], dist2 float64 [n, k]); -1 / -1.0 where the cloud holds fewer than k points (fpcc_knn_points)"""
+    n = query.shape[0]
+    idx = torch.empty((n, k), dtype=torch.int32, device=query.device)
+    d = torch.empty((n, k), dtype=torch.float64, device=query.device)
+    _ok(lib().fpcc_knn_points(grid.ptr, _points3(query, 'query'), n, int(k), idx.data_ptr(), d.data_ptr(), _stream()))
+    return idx, d
+
+
+def nn_points(grid: PointGrid, normals: Optional[torch.Tensor], query: torch.Tensor):
+    """(point-to-plane squared error float64 [n], nearest squared distance float64 [n], nearest row int32 [n]) of every float32 query
+    against the cloud whose rows carry `normals` float64 [m, 3] (None: zero); ties at the nearest distance are averaged (fpcc_nn_points,
+    mode 0)"""
+    n = query.shape[0]
+    plane = torch.empty(n, dtype=torch.float64, device=query.device)
+    d = torch.empty(n, dtype=torch.float64, device=query.device)
+    rows = torch.empty(n, dtype=torch.int32, device=query.device)
+    if normals is not None and tuple(normals.shape) != (grid.points.shape[0], 3):
+        raise ValueError('normals must be float64 [m, 3], one row per point of the cloud')
+    _ok(lib().fpcc_nn_points(grid.ptr, _dev(normals, torch.float64, 'normals', True), _points3(query, 'query'), n, 0, d.data_ptr(),
+                             rows.data_ptr(), plane.data_ptr(), _stream()))
+    return plane, d, rows
+
+
+def pca_normals_points(points: torch.Tensor, nbr: torch.Tensor) -> torch.Tensor:
+    """unit normals float64 [n, 3] from the covariance of the neighbour rows `nbr` int32 [n, k] of float32 `points` [m, 3]
+    (fpcc_pca_normals_points)"""
+    n, k = nbr.shape
+    out = torch.empty((n, 3), dtype=torch.float64, device=nbr.device)
+    _ok(lib().fpcc_pca_normals_points(_points3(points, 'points'), points.shape[0], _dev(nbr, torch.int32, 'nbr', n == 0), n, k,
+                                      out.data_ptr(), _stream()))
+    return out
+
+
+def transfer_normals_points(grid_a: PointGrid, normals_a: torch.Tensor, grid_b: PointGrid) -> torch.Tensor:
+    """pc_error's normals for cloud B from those of cloud A, both float clouds, rows in the callers' order (fpcc_transfer_normals_points)"""
+    n_a, n_b = grid_a.points.shape[0], grid_b.points.shape[0]
+    if tuple(normals_a.shape) != (n_a, 3):
+        raise ValueError('normals_a must be float64 [n_a, 3]')
+    out = torch.empty((n_b, 3), dtype=torch.float64, device=grid_b.points.device)
+    L = lib()
+    need = _ok(L.fpcc_transfer_normals_points_ws_bytes(n_a, n_b))
+    ws = torch.empty(max(need // 8, 2), dtype=torch.int64, device=out.device)
+    _ok(L.fpcc_transfer_normals_points(grid_a.ptr, _points3(grid_a.points, 'points_a'), _dev(normals_a, torch.float64, 'normals_a', n_a == 0),
+                                       grid_b.ptr, _points3(grid_b.points, 'points_b'), out.data_ptr(), ws.data_ptr(), ws.numel() * 8,
+                                       _stream()))
     return out
 
 

@@ -55,11 +55,9 @@ def batched(xyz: np.ndarray, batch: int = 0) -> np.ndarray:
     return np.concatenate((np.full((len(xyz), 1), batch, dtype=np.int32), xyz.astype(np.int32)), 1)
 
 
-def lidar_cloud(seed: int = 3, beams: int = 64, azimuths: int = 2048, resolution: int = 65536, extent: float = 400.0,
-                drop: float = 0.1) -> np.ndarray:
-    """KITTI-like spinning-LiDAR frame (cfg#3): rays cast against a ground plane and random boxes, range noise, dropped
-    returns, quantised as the reference's KITTI loader does (round((p - min) * (resolution - 1) / extent),
-    lib/datasets/KITTIOdometry/dataset.py:91-102).  Returns unique int32 voxels [n, 3]."""
+def lidar_points(seed: int = 3, beams: int = 64, azimuths: int = 2048, drop: float = 0.1) -> np.ndarray:
+    """The returns of a KITTI-like spinning-LiDAR frame in metres, float64 [n, 3], in ray order: rays cast against a ground plane
+    and random boxes, range noise, dropped returns -- the sweep before any quantisation."""
     rng = np.random.default_rng(seed)
     az = np.linspace(0, 2 * np.pi, azimuths, endpoint=False)
     el = np.deg2rad(np.linspace(-24.8, 2.0, beams))
@@ -78,7 +76,14 @@ def lidar_cloud(seed: int = 3, beams: int = 64, azimuths: int = 2048, resolution
         t = np.where(hit & (near < t), near, t)
     ok = np.isfinite(t) & (t < 120)
     ok &= rng.random(len(t)) >= drop
-    p = d[ok] * (t[ok] + rng.normal(0, 0.02, ok.sum()))[:, None]
+    return d[ok] * (t[ok] + rng.normal(0, 0.02, ok.sum()))[:, None]
+
+
+def lidar_cloud(seed: int = 3, beams: int = 64, azimuths: int = 2048, resolution: int = 65536, extent: float = 400.0,
+                drop: float = 0.1) -> np.ndarray:
+    """KITTI-like spinning-LiDAR frame (cfg#3): the returns of `lidar_points`, quantised as the reference's KITTI loader does
+    (round((p - min) * (resolution - 1) / extent), lib/datasets/KITTIOdometry/dataset.py:91-102).  Returns unique int32 voxels [n, 3]."""
+    p = lidar_points(seed, beams, azimuths, drop)
     q = np.round((p - p.min(0)) * ((resolution - 1) / extent)).astype(np.int64)
     key = np.unique((q[:, 0] << 42) | (q[:, 1] << 21) | q[:, 2])
     return np.stack(((key >> 42), (key >> 21) & 0x1fffff, key & 0x1fffff), 1).astype(np.int32)

@@ -654,6 +654,54 @@ int fpcc_transfer_normals(const int64_t *keys_a, int64_t n_a, const int32_t *coo
                           int64_t n_b, const int32_t *coords_b, int bits, double *normals_b_out, void *ws, int64_t ws_bytes, void *stream);
 int fpcc_sum_max_f64(const double *values, int64_t n, double *sum_max_out, void *ws, int64_t ws_bytes, void *stream);
 
+/* The same distortion lines for FLOAT point clouds (metrics_points.hip) -- what the reference obtains from pc_error on the raw LiDAR
+ * sweep (lib/datasets/KITTIOdometry/dataset.py:77-88, lib/evaluators.py:100-108).  Points are float [n][3] rows; duplicated points and
+ * negative coordinates are ordinary input, values must be finite (the caller checks).  "Index" always means a row of the CALLER's
+ * array of the searched cloud.
+ *
+ * A searched cloud is a fpcc_point_grid (a host struct, passed by pointer, device pointers inside): its m points binned into cubic
+ * cells of edge h = 1 / inv_h on a grid of 2^bits cells per axis starting at `origin`,
+ *   keys   = the cell keys of fpcc_point_cell_keys, sorted with fpcc_sort_keys(end_bit = 3 * bits),
+ *   points = the points in that sorted order (caller's points gathered by the sort's perm_out),
+ *   index  = perm_out: the caller's row of every sorted row (NULL = identity).
+ * The grid decides speed only: every result below is the same for any origin, h and bits (as long as the arguments describe the grid
+ * the keys were made with).  m < 2^31.
+ *
+ * fpcc_point_cell_keys: keys_out[i] = Morton code (x on bit 0, batch 0) of the cell of point i, the cell index per axis being
+ *   floor(((double)p - origin) * inv_h) clamped to [0, 2^bits - 1].  origin: 3 doubles on the HOST.
+ * fpcc_knn_points: the k (1..32) nearest points of every query in the total order (d2, index), d2 = (dx*dx + dy*dy) + dz*dz in float64
+ *   with dx = (double)q.x - (double)p.x and every operation rounded on its own (no fused multiply-add): idx_out int32 [n][k], dist2_out
+ *   double [n][k]; -1 and -1.0 where m < k.  A duplicated point is an ordinary member; a point of the cloud finds itself at d2 = 0.
+ * fpcc_nn_points: per query, over ALL points j at the minimum d2 whose normal is a number: mode 0: out[i] = mean_j ((q_i - p_j) .
+ *   normals[j])^2, mode 1: out[3 i ..] = mean_j normals[j]; dist2_out[i] = that minimum (-1.0 if the cloud is empty), nn_index_out[i] =
+ *   the smallest such index (-1 if none).  normals: double [m][3] by INDEX (mode 0: NULL = zero normals); dist2_out, nn_index_out and,
+ *   in mode 0, out may be NULL.
+ * fpcc_pca_normals_points: fpcc_pca_normals for float points: nbr int32 [n][k] holds indices into points [m][3] (the caller's array;
+ *   negative = absent); covariance in float64 relative to the first neighbour, the same closed-form solver, sign rule and (0, 0, 1)
+ *   fallback.
+ * fpcc_transfer_normals_points: fpcc_transfer_normals for float points: points_a / points_b are the caller's arrays of the two clouds
+ *   (rows = indices of grid_a / grid_b), normals_a and normals_b_out by index.  ws: caller-owned, 16-byte aligned,
+ *   fpcc_transfer_normals_points_ws_bytes(n_a, n_b) bytes. */
+typedef struct fpcc_point_grid {
+    const int64_t *keys;
+    const float *points;
+    const int32_t *index;
+    int64_t m;
+    double origin[3];
+    double inv_h;
+    int32_t bits;
+    int32_t reserved;
+} fpcc_point_grid;
+int fpcc_point_cell_keys(const float *points, int64_t n, const double *origin, double inv_h, int bits, int64_t *keys_out, void *stream);
+int fpcc_knn_points(const fpcc_point_grid *grid, const float *query, int64_t n, int k, int32_t *idx_out, double *dist2_out, void *stream);
+int fpcc_nn_points(const fpcc_point_grid *grid, const double *normals, const float *query, int64_t n, int mode, double *dist2_out,
+                   int32_t *nn_index_out, double *out, void *stream);
+int fpcc_pca_normals_points(const float *points, int64_t m, const int32_t *nbr, int64_t n, int k, double *normals_out, void *stream);
+int64_t fpcc_transfer_normals_points_ws_bytes(int64_t n_a, int64_t n_b);
+int fpcc_transfer_normals_points(const fpcc_point_grid *grid_a, const float *points_a, const double *normals_a,
+                                 const fpcc_point_grid *grid_b, const float *points_b, double *normals_b_out, void *ws, int64_t ws_bytes,
+                                 void *stream);
+
 /* Recolouring target of the colour codec's training loss -- replaces `sample_wise_recolor`, a knn3d search in both directions plus
  * masked tensor ops (models/convolutional/lossy_coord_lossy_color/layers.py:269-333).  pred_keys: the m kept reconstructed voxels,
  * tgt_keys: the n original voxels, both SORTED unique key sets of `bits` bits per axis with the sample index above the Morton bits
