@@ -38,7 +38,8 @@ constexpr int kMaxRefill = 3;         // bytes a decoder may shift in per symbol
 
 // a quantised CDF the coders accept: starts at 0, strictly increasing, ends at 2^16
 bool cdf_well_formed(const uint32_t *c, int64_t len) {
-    if (len < 2 || c[0] != 0 || c[len - 1] != kProbOne) return false;
+    if (len < 2 || len > int64_t(kProbOne) + 1) return false;          // (more edges than values cannot increase: not read at all)
+    if (c[0] != 0 || c[len - 1] != kProbOne) return false;
     for (int64_t i = 1; i < len; ++i) if (c[i] <= c[i - 1]) return false;
     return true;
 }
@@ -79,6 +80,9 @@ public:
     // shifts out 0, 1 or 2 bytes (x < 2^31, the ceiling >= 2^15 * freq), which of them is as good as random to the branch predictor
     // -- the loop above spends more on mispredictions than on arithmetic.  Both bytes are stored below the write position whether or
     // not they are emitted; what is not emitted is overwritten by the next symbol or by finish().
+    // Memory-safe for ANY start and any freq in [0, 65536] (callers that validate after the loop rely on it): the reciprocal is read
+    // inside the table (m[0] == 0), at most two bytes leave per call, and the arithmetic is unsigned -- an invalid range only yields
+    // a state no decoder can read, which those callers discard.
     template <uint32_t BITS>
     inline void put_roomy(uint32_t start, uint32_t freq) {
         static_assert(BITS == 16, "the byte count below is derived for 16-bit frequencies");
@@ -175,6 +179,16 @@ struct Tables {
     int64_t count;
 };
 
+// what both indexed coders ask of their tables, once per call: a length no mode can use (fewer than two edges) is an invalid
+// argument, a table of edges that is not a quantised CDF is E_CDF.  Two edges are one bin: in overflow mode the escape bin alone.
+int64_t check_tables(const Tables &t) {
+    for (int64_t ti = 0; ti < t.count; ++ti) {
+        if (t.len[ti] < 2) return FPCC_HOST_E_ARG;
+        if (!cdf_well_formed(t.cdf + t.start[ti], t.len[ti])) return FPCC_HOST_E_CDF;
+    }
+    return FPCC_HOST_OK;
+}
+
 template <bool ESCAPE>
 int64_t indexed_encode(const int32_t *sym, const int32_t *index, int64_t n, const Tables &t, uint8_t *out, int64_t cap) {
     BackWriter w(out, cap);
@@ -183,14 +197,16 @@ int64_t indexed_encode(const int32_t *sym, const int32_t *index, int64_t n, cons
         if (ti < 0 || ti >= t.count) return FPCC_HOST_E_ARG;
         const uint32_t *c = t.cdf + t.start[ti];
         const int32_t bins = static_cast<int32_t>(t.len[ti]) - 1;
-        int32_t v = sym[i] - t.offsets[ti];
+        int64_t v = int64_t(sym[i]) - t.offsets[ti];                   // 64-bit: the difference of two int32 need not be one
         if (ESCAPE) {
             // Values outside [0, bins-2] go through the last bin followed by an Elias-gamma-like tail of 1-bit
-            // uniform symbols.  Pushed in reverse of the decoder's reading order.
-            const int32_t esc = bins - 1;
+            // uniform symbols.  Pushed in reverse of the decoder's reading order.  The format carries an int32 difference
+            // (magnitudes up to 2^31): anything wider is refused
+            if (v < INT32_MIN || v > INT32_MAX) return FPCC_HOST_E_ARG;
+            const int64_t esc = bins - 1;
             const bool neg = v < 0;
             uint32_t mag = 0;
-            if (neg) { mag = static_cast<uint32_t>(-static_cast<int64_t>(v)); v = esc; }
+            if (neg) { mag = static_cast<uint32_t>(-v); v = esc; }
             else if (v >= esc) { mag = static_cast<uint32_t>(v - esc + 1); v = esc; }
             if (v == esc) {
                 w.put<1>(neg ? 1u : 0u, 1u);
@@ -225,7 +241,7 @@ int64_t single_table_decode(const uint8_t *stream, int64_t stream_len, int64_t n
         for (; i < next_mark; ++i) {
             const uint32_t v = slot_to_bin[r.peek<kProbBits>()];
             r.take<kProbBits>(c[v], c[v + 1] - c[v]);
-            out[i] = static_cast<int32_t>(v) + offset;
+            out[i] = static_cast<int32_t>(v + static_cast<uint32_t>(offset));      // (unsigned: wraps, never overflows)
         }
         if (progress) progress->store(i, std::memory_order_release);
         next_mark = std::min<int64_t>(n, next_mark + 4096);
@@ -237,8 +253,7 @@ template <bool ESCAPE>
 int64_t indexed_decode(const uint8_t *stream, int64_t stream_len, const int32_t *index, int64_t n, const Tables &t,
                        int32_t *out) {
     if (stream_len < 4) return FPCC_HOST_E_ARG;
-    for (int64_t ti = 0; ti < t.count; ++ti)
-        if (!cdf_well_formed(t.cdf + t.start[ti], t.len[ti])) return FPCC_HOST_E_CDF;
+    if (const int64_t rc = check_tables(t)) return rc;
     if (!ESCAPE && t.count == 1 && n >= 8192 && t.len[0] - 1 <= 65535)
         return single_table_decode(stream, stream_len, n, t.cdf + t.start[0], static_cast<int32_t>(t.len[0]) - 1,
                                    t.offsets[0], out);
@@ -260,17 +275,21 @@ int64_t indexed_decode(const uint8_t *stream, int64_t stream_len, const int32_t 
                 if (++width > 31) return FPCC_HOST_E_ARG;      // no int32 magnitude is that wide: corrupt stream
             }
             r.take<1>(1u, 1u);
-            int32_t mag = 1;
+            uint32_t mag = 1;                                      // up to 32 bits wide: -2^31 has the magnitude 2^31
             for (int b = 0; b < width; ++b) {
                 const uint32_t bit = r.peek<1>();
                 r.take<1>(bit, 1u);
-                mag = (mag << 1) | static_cast<int32_t>(bit);
+                mag = (mag << 1) | bit;
             }
             const uint32_t neg = r.peek<1>();
             r.take<1>(neg, 1u);
-            v = neg ? -mag : mag + (bins - 1) - 1;
+            const int64_t wide = (neg ? -int64_t(mag) : int64_t(mag) + (bins - 1) - 1) + t.offsets[ti];
+            if (wide < INT32_MIN || wide > INT32_MAX) return FPCC_HOST_E_ARG;      // no encoder writes that: corrupt stream
+            out[i] = static_cast<int32_t>(wide);
+            continue;
         }
-        out[i] = v + t.offsets[ti];
+        // (unsigned: a table whose offset puts a bin past the int32 range wraps instead of overflowing)
+        out[i] = static_cast<int32_t>(static_cast<uint32_t>(v) + static_cast<uint32_t>(t.offsets[ti]));
     }
     return FPCC_HOST_OK;
 }
@@ -287,7 +306,9 @@ int64_t binary_encode(const uint8_t *bits, const uint16_t *p1, int64_t n, uint8_
             bad |= uint32_t(p == 0);
             const uint32_t mask = 0u - uint32_t(bits[i] != 0);
             const uint32_t split = kProbOne - p;
-            w.put_roomy<kProbBits>(split & mask, ((p & mask) | (split & ~mask)) | uint32_t(p == 0));     // (a zero probability: any valid frequency; the result is discarded)
+            // a zero probability makes the frequency 0 (a one) or 65536 (a zero): both index kRcp inside its 65537 entries, the step
+            // shifts out at most its two budgeted bytes either way, and the result is discarded below
+            w.put_roomy<kProbBits>(split & mask, (p & mask) | (split & ~mask));
         }
         if (bad) return FPCC_HOST_E_ARG;
         return w.finish();
@@ -371,8 +392,9 @@ int64_t fpcc_pmf_to_quantized_cdf(const double *pmf, int64_t n, int overflow, in
 int64_t fpcc_rans_indexed_encode(const int32_t *symbols, const int32_t *index, int64_t n, const uint32_t *cdf,
                                  const int64_t *cdf_start, const int64_t *cdf_len, const int32_t *offsets,
                                  int64_t n_tables, int overflow, uint8_t *out, int64_t cap) {
-    if (!symbols || !cdf || !cdf_start || !cdf_len || !offsets || !out || n < 0 || n_tables < 1) return FPCC_HOST_E_ARG;
+    if (!symbols || !cdf || !cdf_start || !cdf_len || !offsets || !out || n < 0 || n_tables < 1 || cap < 0) return FPCC_HOST_E_ARG;
     const Tables t{cdf, cdf_start, cdf_len, offsets, n_tables};
+    if (const int64_t rc = check_tables(t)) return rc;               // as the decoder does: the symbol loop indexes them unchecked
     return overflow ? indexed_encode<true>(symbols, index, n, t, out, cap)
                     : indexed_encode<false>(symbols, index, n, t, out, cap);
 }
@@ -388,7 +410,7 @@ int64_t fpcc_rans_indexed_decode(const uint8_t *stream, int64_t stream_len, cons
 }
 
 int64_t fpcc_rans_binary_encode(const uint8_t *bits, const uint16_t *prob1, int64_t n, uint8_t *out, int64_t cap) {
-    if (!bits || !prob1 || !out || n < 0) return FPCC_HOST_E_ARG;
+    if (!bits || !prob1 || !out || n < 0 || cap < 0) return FPCC_HOST_E_ARG;
     return binary_encode(bits, prob1, n, out, cap);
 }
 
@@ -431,7 +453,10 @@ int64_t fpcc_rans_binary_decode(const uint8_t *stream, int64_t stream_len, const
 int64_t fpcc_rans_binary_encode_multi(const uint8_t *bits, const uint16_t *prob1, const int64_t *start,
                                       int64_t n_streams, uint8_t *out, int64_t cap_each, int64_t *len_out,
                                       int n_threads) {
-    if (!bits || !prob1 || !start || !out || !len_out || n_streams < 0) return FPCC_HOST_E_ARG;
+    if (!bits || !prob1 || !start || !out || !len_out || n_streams < 0 || cap_each < 0) return FPCC_HOST_E_ARG;
+    if (n_streams > 0 && start[0] < 0) return FPCC_HOST_E_ARG;
+    for (int64_t s = 0; s < n_streams; ++s)
+        if (start[s + 1] < start[s]) return FPCC_HOST_E_ARG;          // a negative length would be coded as an empty stream
     std::atomic<int64_t> next{0};
     auto work = [&]() {
         for (;;) {
@@ -654,7 +679,7 @@ void fpcc_simple_enc_free(fpcc_simple_enc *e) { delete e; }
 
 int64_t fpcc_simple_enc_push(fpcc_simple_enc *e, const uint16_t *rows, int64_t n_rows, int64_t width,
                              const uint16_t *symbols, int64_t n) {
-    if (!e || !rows || !symbols || width < 1 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
+    if (!e || !rows || !symbols || width < 1 || n < 0 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
     for (int64_t i = n - 1; i >= 0; --i) {
         const uint16_t *row = rows + (n_rows == 1 ? 0 : i * width);
         const uint32_t s = symbols[i];
@@ -668,22 +693,35 @@ int64_t fpcc_simple_enc_push(fpcc_simple_enc *e, const uint16_t *rows, int64_t n
 }
 
 int64_t fpcc_simple_enc_push_bin(fpcc_simple_enc *e, const uint16_t *edge, int64_t n_rows, const uint8_t *bits, int64_t n) {
-    if (!e || !edge || !bits || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
+    if (!e || !edge || !bits || n < 0 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
     for (int64_t i = n - 1; i >= 0; --i) {
         const uint32_t c = edge[n_rows == 1 ? 0 : i];
         if (bits[i]) e->w.put<kProbBits>(c, kProbOne - c);
+        else if (c == 0) return FPCC_HOST_E_ARG;                      // a zero below an edge of 0: no range to code it in
         else e->w.put<kProbBits>(0u, c);
     }
     return e->w.full() ? int64_t(FPCC_HOST_E_BUFFER) : e->w.buffered();
 }
 
 int64_t fpcc_simple_enc_push_ranges(fpcc_simple_enc *e, const uint16_t *start, const uint16_t *freq_m1, int64_t n) {
-    if (!e || !start || !freq_m1) return FPCC_HOST_E_ARG;
+    if (!e || !start || !freq_m1 || n < 0) return FPCC_HOST_E_ARG;
+    // a range must end inside the interval: start + freq <= 65536, i.e. start + freq_m1 fits in 16 bits.  Accumulated, not branched
+    // on, as in binary_encode: both steps are memory-safe for a range that does not, and the stream is discarded
+    uint32_t bad = 0;
     if (e->w.room(2 * n + 8)) {
-        for (int64_t i = n - 1; i >= 0; --i) e->w.put_roomy<kProbBits>(start[i], uint32_t(freq_m1[i]) + 1u);
+        for (int64_t i = n - 1; i >= 0; --i) {
+            const uint32_t s = start[i], f = freq_m1[i];
+            bad |= (s + f) >> 16;
+            e->w.put_roomy<kProbBits>(s, f + 1u);
+        }
     } else {
-        for (int64_t i = n - 1; i >= 0; --i) e->w.put<kProbBits>(start[i], uint32_t(freq_m1[i]) + 1u);
+        for (int64_t i = n - 1; i >= 0; --i) {
+            const uint32_t s = start[i], f = freq_m1[i];
+            bad |= (s + f) >> 16;
+            e->w.put<kProbBits>(s, f + 1u);
+        }
     }
+    if (bad) return FPCC_HOST_E_ARG;
     return e->w.full() ? int64_t(FPCC_HOST_E_BUFFER) : e->w.buffered();
 }
 
@@ -708,7 +746,7 @@ void fpcc_simple_dec_free(fpcc_simple_dec *d) { delete d; }
 
 int64_t fpcc_simple_dec_pop(fpcc_simple_dec *d, const uint16_t *rows, int64_t n_rows, int64_t width,
                             uint16_t *symbols_out, int64_t n) {
-    if (!d || !rows || !symbols_out || width < 1 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
+    if (!d || !rows || !symbols_out || width < 1 || n < 0 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
     constexpr int64_t kAhead = 6;                       // rows requested ahead of the one being searched
     const int64_t row_bytes = width * 2;
     const bool wide = kHaveAvx512 && width >= 64;
@@ -742,7 +780,7 @@ int64_t fpcc_simple_dec_tell(const fpcc_simple_dec *d, uint32_t *state_out, int6
 }
 
 int64_t fpcc_simple_dec_pop_bin(fpcc_simple_dec *d, const uint16_t *edge, int64_t n_rows, uint8_t *bits_out, int64_t n) {
-    if (!d || !edge || !bits_out || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
+    if (!d || !edge || !bits_out || n < 0 || (n_rows != 1 && n_rows != n)) return FPCC_HOST_E_ARG;
     for (int64_t i = 0; i < n; ++i) {
         const uint32_t c = edge[n_rows == 1 ? 0 : i];
         const bool one = d->r.peek<kProbBits>() >= c;
@@ -826,7 +864,7 @@ void fpcc_pool_free(fpcc_pool *p) { delete p; }
 
 int64_t fpcc_pool_binary_encode(fpcc_pool *p, const volatile uint32_t *flag, uint32_t ready, const uint8_t *bits,
                                 const uint16_t *prob1, int64_t n, uint8_t *out, int64_t cap, int64_t *len_out) {
-    if (!p || !bits || !prob1 || !out || !len_out || n < 0) return FPCC_HOST_E_ARG;
+    if (!p || !bits || !prob1 || !out || !len_out || n < 0 || cap < 0) return FPCC_HOST_E_ARG;
     p->submit([=]() -> int64_t {
         if (!await_flag(flag, ready)) return *len_out = FPCC_HOST_E_TIMEOUT;
         return *len_out = binary_encode(bits, prob1, n, out, cap);
@@ -837,7 +875,7 @@ int64_t fpcc_pool_binary_encode(fpcc_pool *p, const volatile uint32_t *flag, uin
 int64_t fpcc_pool_histogram_encode(fpcc_pool *p, const volatile uint32_t *flag, uint32_t ready, const int32_t *symbols,
                                    int64_t n, int fixed_offset, int32_t *offset_io, uint32_t *cdf_out, int64_t cdf_cap,
                                    int64_t *cdf_len_out, uint8_t *out, int64_t cap, int64_t *len_out) {
-    if (!p || !symbols || !offset_io || !cdf_out || !cdf_len_out || !out || !len_out || n < 1 || cdf_cap < 2)
+    if (!p || !symbols || !offset_io || !cdf_out || !cdf_len_out || !out || !len_out || n < 1 || cdf_cap < 2 || cap < 0)
         return FPCC_HOST_E_ARG;
     p->submit([=]() -> int64_t {
         if (!await_flag(flag, ready)) return *len_out = FPCC_HOST_E_TIMEOUT;

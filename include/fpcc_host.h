@@ -35,7 +35,12 @@ int64_t fpcc_pmf_to_quantized_cdf(const double *pmf, int64_t n, int overflow, in
 /* Replaces IndexedRansCoder::{encode, encode_with_indexes, decode, decode_with_indexes} for ONE batch unit
  * (rans_wrapper.cpp:89-185,206-279).  Tables are flattened: table t = cdf[cdf_start[t] .. cdf_start[t]+cdf_len[t]),
  * cdf[0] == 0, last == 65536.  index == NULL selects table (i % n_tables) as the reference's non-indexed mode does.
- * Encode writes the stream at the END of out[0..cap) and returns its length. */
+ * Encode writes the stream at the END of out[0..cap) and returns its length.
+ * Both directions check every table once per call: cdf_len < 2 is FPCC_HOST_E_ARG, a table that does not start at 0, end at
+ * 65536 and increase strictly in between is FPCC_HOST_E_CDF (two edges are one bin; in overflow mode that is the escape bin alone).
+ * FPCC_HOST_E_ARG as well: a table index outside [0, n_tables); without overflow a symbol outside its table; with overflow a
+ * symbol whose (symbol - offset) is not an int32 -- every difference that is one round-trips, INT32_MIN included.  The decoder
+ * returns FPCC_HOST_E_ARG for a stream that is shorter than 4 bytes, starts below 2^23 or escapes to a value outside int32. */
 int64_t fpcc_rans_indexed_encode(const int32_t *symbols, const int32_t *index, int64_t n,
                                  const uint32_t *cdf, const int64_t *cdf_start, const int64_t *cdf_len,
                                  const int32_t *offsets, int64_t n_tables, int overflow,
@@ -45,7 +50,8 @@ int64_t fpcc_rans_indexed_decode(const uint8_t *stream, int64_t stream_len, cons
                                  const int32_t *offsets, int64_t n_tables, int overflow, int32_t *symbols_out);
 
 /* Replaces BinaryRansCoder::{encode, decode} for one batch unit (rans_wrapper.cpp:326-382,385-428).
- * prob1[i] = P(bit i == 1) * 65536, in [1, 65535]. */
+ * prob1[i] = P(bit i == 1) * 65536, in [1, 65535].  A zero probability anywhere is FPCC_HOST_E_ARG, whatever the bit and
+ * however much room `out` has; a stream that does not fit is FPCC_HOST_E_BUFFER; a negative cap is FPCC_HOST_E_ARG. */
 int64_t fpcc_rans_binary_encode(const uint8_t *bits, const uint16_t *prob1, int64_t n, uint8_t *out, int64_t cap);
 int64_t fpcc_rans_binary_decode(const uint8_t *stream, int64_t stream_len, const uint16_t *prob1, int64_t n,
                                 uint8_t *bits_out);
@@ -53,7 +59,8 @@ int64_t fpcc_rans_binary_decode(const uint8_t *stream, int64_t stream_len, const
 /* Several independent binary streams at once, one host thread each (the reference's OpenMP-over-batch loop,
  * rans_wrapper.cpp:340-341, used here across the occupancy levels of one frame).  Stream s covers
  * bits[start[s] .. start[s+1]).  Its bytes are written at the END of out + s*cap_each .. +cap_each; len_out[s] gets the
- * length or a negative error code.  Returns 0 or the first error. */
+ * length or a negative error code.  Returns 0 or the first error.  start[] must not decrease and start[0] >= 0:
+ * FPCC_HOST_E_ARG otherwise, before anything is coded. */
 int64_t fpcc_rans_binary_encode_multi(const uint8_t *bits, const uint16_t *prob1, const int64_t *start, int64_t n_streams,
                                       uint8_t *out, int64_t cap_each, int64_t *len_out, int n_threads);
 
@@ -90,7 +97,11 @@ int64_t fpcc_progress_wait(const int64_t *progress, int64_t needed);
 int64_t fpcc_pool_wait(fpcc_pool *p);
 
 /* Replaces RansEncoder / RansDecoder of simple_rans_ext_cpp: one persistent stream, blocks pushed LIFO.
- * rows: uint16 [n_rows, width], entry s = upper edge of symbol s, last edge implicitly 65536; n_rows == n or 1. */
+ * rows: uint16 [n_rows, width], entry s = upper edge of symbol s, last edge implicitly 65536; n_rows == n or 1.
+ * A push returns the bytes buffered so far, FPCC_HOST_E_BUFFER once the encoder's buffer is full, or FPCC_HOST_E_ARG for a symbol
+ * that has no range: push -- symbol >= width, or a row that does not increase at the coded symbol; push_bin -- a zero bit under
+ * edge == 0; push_ranges -- start + freq_m1 + 1 > 65536.  After a failed push the encoder's content is unspecified until
+ * fpcc_simple_enc_finish, which is always safe to call, resets it; the next block is then coded as by a new encoder. */
 typedef struct fpcc_simple_enc fpcc_simple_enc;
 typedef struct fpcc_simple_dec fpcc_simple_dec;
 fpcc_simple_enc *fpcc_simple_enc_new(int64_t buf_bytes);
