@@ -1727,15 +1727,18 @@ class _Requant8(C.Structure):
 
 def _also8(also, n: int, c_out: int, device):
     """also: sequence of (requant_mul uint32[1], zero_point int64[1], shift, width) -- one extra int8 copy of an int32 result per
-    consumer requantiser; width >= c_out is the row stride of the buffer (columns past c_out belong to the caller).  Returns the
-    ctypes array, its length and the int8 tensors [n, width]."""
+    consumer requantiser; width >= c_out is the row stride of the buffer (columns past c_out belong to the caller).  An optional
+    fifth element is a preallocated contiguous int8 [n, width] tensor to write into instead of a fresh one.  Returns the ctypes
+    array, its length and the int8 tensors [n, width]."""
     if not also:
         return None, 0, []
     arr = (_Requant8 * len(also))()
     outs = []
     keep = []          # converted multipliers: a temporary freed before the launch could be handed out again by the caching allocator
-    for i, (mul, zp, shift, width) in enumerate(also):
-        buf = torch.empty((n, width), dtype=torch.int8, device=device)
+    for i, (mul, zp, shift, width, *given) in enumerate(also):
+        buf = given[0] if given else torch.empty((n, width), dtype=torch.int8, device=device)
+        if given and (buf.dtype != torch.int8 or tuple(buf.shape) != (n, width) or not buf.is_contiguous() or buf.device != device):
+            raise ValueError('a preallocated extra output must be a contiguous int8 [n, width] tensor on the device of the result')
         m = _mul_u32(mul)
         keep.append(m)
         arr[i].out, arr[i].ld, arr[i].pad = buf.data_ptr(), width, c_out

@@ -98,6 +98,7 @@ def test_pyramid_and_neighbour_tables(ops, res, n):
         assert rows.shape == (lvl_l.n, 32) and torch.equal(rows[:, :27], nbr.t()) and bool((rows[:, 27:] == -1).all())
         want_masks = ((want >= 0).astype(np.int64) << np.arange(27)[:, None]).sum(0)
         assert (masks.cpu().numpy().astype(np.int64) == want_masks).all()
+        assert torch.equal(ops.mask27_from_parent(keys_l, parent_of, parent_nbr, child_row), masks)       # the masks without the table
         order_t = ops.conv_row_order(nbr, 27, lvl_l.n, 1, lvl_l.n, 13)
         order_m = ops.conv_row_order(None, 27, lvl_l.n, 1, lvl_l.n, 13, masks=masks)
         assert torch.equal(order_t, order_m)
@@ -210,3 +211,86 @@ def test_hilbert_keys_match_reference_golden_and_oracle():
     got = ops.hilbert3d_encode(torch.from_numpy(big).cuda(), 21, (1, 2, 3)).cpu().numpy()
     assert (got == hilbert3d_encode(big, 21, (1, 2, 3))).all()
     assert ops.hilbert3d_encode(torch.zeros((0, 3), dtype=torch.int32, device='cuda'), 10).shape == (0,)
+
+
+def _octree_children_reference(symbols, coords):
+    """OracleInt._bits and OracleInt._children (oracle/codec_int.py) on plain arrays: bit k of a row = bit (7 - k) of symbol + 1;
+    children in row-major order of the bits, child k of (b, x, y, z) = (b, 2x + (k >> 2), 2y + ((k >> 1) & 1), 2z + (k & 1))"""
+    bin2oct = np.arange(7, -1, -1)
+    bits = (((symbols.astype(np.int64)[:, None] + 1) >> bin2oct) & 1).astype(bool)
+    unfold = np.array([(0, dx, dy, dz) for dx in (0, 1) for dy in (0, 1) for dz in (0, 1)], dtype=np.int64)[None]
+    c = coords.astype(np.int64)[:, None].copy()
+    c[..., 1:] <<= 1
+    parent_row, octant = np.nonzero(bits)
+    return bits, (c + unfold)[bits], parent_row, octant
+
+
+@pytest.mark.parametrize('case', ['every_symbol', 'one_full_parent', 'random'])
+def test_octree_children_match_the_oracle(ops, case):
+    """fpcc_octree_children, one octree step of the integer codec, from symbols and from bits, with and without coordinates and table"""
+    rng = np.random.default_rng(7)
+    if case == 'every_symbol':
+        symbols = rng.permutation(255).astype(np.int16)
+    elif case == 'one_full_parent':
+        symbols = np.array([254], np.int16)
+    else:
+        symbols = rng.integers(0, 255, 1000).astype(np.int16)
+    n = len(symbols)
+    coords = np.concatenate((rng.integers(0, 3, (n, 1)), rng.integers(0, 1 << 12, (n, 3))), 1).astype(np.int32)
+    bits, children, parent_row, octant = _octree_children_reference(symbols, coords)
+    m = len(parent_row)
+    assert m == (8 if case == 'one_full_parent' else m) and (case != 'every_symbol' or sorted(symbols.tolist()) == list(range(255)))
+    fxp_one = 1 << 23
+    want_table = np.zeros(((m + 127) // 128 * 128, 8), np.int32)
+    want_table[np.arange(m), octant] = parent_row + 1
+    sym_d, bits_d, coords_d = _dev(symbols), _dev(bits.astype(np.uint8)), _dev(coords)
+    for source in (dict(symbols=sym_d), dict(bits=bits_d)):
+        for with_coords in (False, True):
+            for want_tab in (True, False):
+                d = ops.octree_children(n, m, coords=coords_d if with_coords else None, fxp_one=fxp_one, want_table=want_tab, **source)
+                got = {k: v.cpu().numpy() for k, v in d.items()}
+                assert set(got) == {'parent_row', 'octant', 'bits', 'fxp'} | ({'table'} if want_tab else set()) | \
+                    ({'child_coords'} if with_coords else set())
+                assert (got['bits'] == bits).all() and got['bits'].dtype == np.uint8
+                assert (got['fxp'] == bits.astype(np.int32) * fxp_one).all()
+                assert (got['parent_row'] == parent_row).all() and (got['octant'] == octant).all()
+                if with_coords:
+                    assert (got['child_coords'] == children).all()
+                if want_tab:
+                    assert got['table'].shape == want_table.shape and (got['table'] == want_table).all()
+
+
+@pytest.mark.parametrize('clouds', [1, 3])
+def test_level_counts_of_a_batch_equal_each_clouds_own(ops, clouds):
+    """fpcc_level_histogram_clouds (keys = cloud << 48 | Morton code, cloud-major) = fpcc_level_histogram of every cloud's own keys = the
+    distinct coarsened codes counted in NumPy"""
+    rng = np.random.default_rng(clouds)
+    levels, per_cloud = 6, []
+    for c in range(clouds):
+        morton = np.unique(rng.integers(0, 1 << 21, 4000 + 1500 * c))
+        per_cloud.append((np.int64(c) << 48) | morton.astype(np.int64))
+    got = ops.level_counts_clouds(_dev(np.concatenate(per_cloud)), levels, 48, clouds)
+    assert len(got) == levels + 1 and all(len(row) == clouds for row in got)
+    for c, keys in enumerate(per_cloud):
+        own = ops.level_counts(_dev(keys), levels)
+        want = [len(np.unique(keys >> (3 * l))) for l in range(levels + 1)]
+        assert [len(keys)] + own == want
+        assert [got[l][c] for l in range(levels + 1)] == want
+
+
+@pytest.mark.parametrize('n', [0, 1, 70001])
+def test_gather_rows_of_a_strided_matrix(ops, n):
+    """fpcc_gather_rows_f32 on a column slice (row stride > width) with repeated indices = index_select, bit for bit"""
+    rng = np.random.default_rng(n)
+    full = torch.from_numpy(rng.normal(size=(5000, 40)).astype(np.float32)).cuda()
+    full[3, 7] = float('nan')
+    full[4, 8] = -0.0
+    x = full[:, 3:35]
+    assert x.stride(0) == 40 and not x.is_contiguous()
+    index = torch.from_numpy(rng.integers(0, 5000, n).astype(np.int32)).cuda()
+    if n > 1:
+        index[:4] = torch.tensor([3, 3, 4, 4999], dtype=torch.int32)
+    got = ops.gather_rows(x, index)
+    want = x.index_select(0, index.long())
+    assert got.shape == (n, 32) and got.dtype == torch.float32
+    assert torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
