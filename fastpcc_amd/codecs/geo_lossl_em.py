@@ -27,7 +27,7 @@ from .._native import host, host_check
 from ..bitstream import BytesListUtils, bytes_to_int, int_to_bytes
 from ..coder_pool import CoderPool
 from ..entropy_models import NoisyDeepFactorizedEntropyModel
-from ..rans_coder import BinaryRansCoder, IndexedRansCoder
+from ..rans_coder import BinaryRansCoder, IndexedRansCoder, InterleavedBinaryCoder
 
 
 class GeoLosslessEntropyModel(nn.Module):
@@ -69,6 +69,12 @@ class GeoLosslessEntropyModel(nn.Module):
         # but the 4-byte count of occupied children leaves the GPU per level.  Same result; slower than the host path on the
         # large levels (profiles/r02/device_rans.md), hence off by default.
         self.device_decoder = False
+        # 'reference': the occupancy levels are the reference's single-state binary streams, coded and decoded on host threads (above).
+        # 'interleaved': every level is coded ON THE DEVICE into interleaved blocks ("Interleaved occupancy blocks";
+        # hipops.rans_binary_il_encode_dev) -- masks and probabilities never leave the GPU, the blocks and their lengths travel on the
+        # side stream -- and the stream says so in bit 7 of its level count.  Encoder option only: the decoder reads the format from
+        # the stream.  defer_occupancy / occupancy_stream keep working in this mode (same blocks in any order of evaluation).
+        self.occupancy_format = 'reference'
         self.timing = None          # set to a dict to collect host-side wall-clock marks (seconds) of the last call
 
     # -- rANS of an integer array under its own histogram (geo_lossl_em.py:59-93) -------------------------------------
@@ -251,6 +257,10 @@ class GeoLosslessEntropyModel(nn.Module):
                          default=len(feas))
         last_residual = min((i for i in range(len(feas)) if i > self.skip_encoding_fea), default=len(feas))
         residual_job = None
+        if self.occupancy_format not in ('reference', 'interleaved'):
+            raise ValueError("occupancy_format must be 'reference' or 'interleaved'")
+        interleaved = self.occupancy_format == 'interleaved'
+        occupancy_il = []        # interleaved: (blocks u8, lengths + status i64, block offsets, cloud ranges) per coded level, host side
 
         def ship_residuals():
             """all residual symbols in ONE copy, cloud-major (a cloud's stream holds its rows of every level, coarse level first),
@@ -280,10 +290,21 @@ class GeoLosslessEntropyModel(nn.Module):
         def code_occupancy(idx: int, lower_of_level: ME.SparseTensor, target_map) -> None:
             nonlocal n_flags
             logits = self.hyper_decoder_coord[idx](lower_of_level)       # on the 8 candidate children of every voxel
+            cand = [8 * e for e in edges_of(target_map.parent)]          # the candidates of a cloud: 8 per row of the level above
+            if interleaved:
+                # coded where the symbols are: one wave per chunk, one block per cloud; only the blocks (at their worst-case offsets) and
+                # their lengths go to the host, with no flag -- nothing on the host waits for them before the encoder's one blocking point
+                mask_d, prob_d = ops.child_mask(target_map.child_row), ops.logit_to_prob16(logits.F.view(-1))
+                blocks_d, meta_d, offsets = ops.rans_binary_il_encode_dev(mask_d, prob_d, cand)
+                blocks_h, meta_h = self._ship(st, [blocks_d, meta_d], None)
+                occupancy_il.append((blocks_h, meta_h, offsets, cand))
+                if self.keep_symbols:                                    # test hook only: the symbols themselves, as the host path keeps them
+                    mask_h, prob_h = self._ship(st, [mask_d, prob_d], None)
+                    occupancy_h.append((mask_h, prob_h.view(np.uint16), cand))
+                return
             mask_h, prob_h = self._ship(st, [ops.child_mask(target_map.child_row),
                                              ops.logit_to_prob16(logits.F.view(-1))], n_flags)
             prob_h = prob_h.view(np.uint16)
-            cand = [8 * e for e in edges_of(target_map.parent)]          # the candidates of a cloud: 8 per row of the level above
             for c in range(B):
                 pool.binary_encode(mask_h[cand[c]:cand[c + 1]], prob_h[cand[c]:cand[c + 1]], flags[n_flags:n_flags + 1])
             n_flags += 1
@@ -372,15 +393,21 @@ class GeoLosslessEntropyModel(nn.Module):
             GeoLosslessEntropyModel.handover_retries += 1
             import warnings
             warnings.warn('coder pool job failed and succeeded when repeated after a synchronise: ' + note)
-        n_levels = len(occupancy_h)
+        n_levels = len(occupancy_il) if interleaved else len(occupancy_h)
         by_level = [streams[l * B:(l + 1) * B] for l in range(n_levels)]
+        st['side'].synchronize()
+        if 'occ' in st:
+            st['occ'].synchronize()
+        if interleaved:                                                  # the copies have landed: cut the blocks out of their worst-case slots
+            by_level = []
+            for blocks_h, meta_h, offsets, _ in occupancy_il:
+                if int(meta_h[B]) != 0:
+                    raise RuntimeError('occupancy level with a zero probability: not codable')
+                by_level.append([blocks_h[offsets[c]: offsets[c] + int(meta_h[c])].tobytes() for c in range(B)])
         if pending_occ:                                                  # coded finest first: back to level order (coarse -> fine)
             by_level.reverse()
             occupancy_h.reverse()
             pending_occ.clear()
-        st['side'].synchronize()
-        if 'occ' in st:
-            st['occ'].synchronize()
         if tm is not None:
             tm['enc_synced'] = tm['enc_occupancy_coded'] = time.perf_counter()
         if self.keep_symbols:      # test hook: what went into the coders
@@ -403,7 +430,7 @@ class GeoLosslessEntropyModel(nn.Module):
                 sym_h, job = residual_job[c]
                 offset, cdf, payload = pool.histogram_result(job)
                 self._write_coded(bs, sym_h.size, offset, cdf, payload, True)
-                bs.write(int_to_bytes(n_levels, 1))
+                bs.write(int_to_bytes(n_levels | (0x80 if interleaved else 0), 1))      # bit 7: the levels are interleaved blocks
                 BytesListUtils.concat_bytes_list([level[c] for level in by_level], bs)
                 self.rans_encode_with_cdf(xyz_h[bottom_edges[c]:bottom_edges[c + 1]], bs, 0)
                 out.append(bs.getvalue())
@@ -470,9 +497,10 @@ class GeoLosslessEntropyModel(nn.Module):
                 bottom_rows = bytes_to_int(bs.read(self.broadcast_shape_bytes))
                 n_sym, sym_offset, sym_cdf, sym_payload = self._read_coded(bs, None)
                 n_streams = bytes_to_int(bs.read(1))
+                il_blocks, n_streams = n_streams >> 7, n_streams & 0x7f     # bit 7: interleaved blocks (no reference stream sets it)
                 coord_bytes_list = BytesListUtils.split_bytes_list(None, n_streams, bs) if n_streams else []
                 bottom_xyz, _ = self.rans_decode_with_cdf(bs, 0, 3)
-            parsed.append((bottom_level, bottom_rows, n_sym, sym_offset, sym_cdf, sym_payload, coord_bytes_list, bottom_xyz))
+            parsed.append((bottom_level, bottom_rows, n_sym, sym_offset, sym_cdf, sym_payload, coord_bytes_list, bottom_xyz, il_blocks))
         # every residual symbol lies in its stream's alphabet: [offset, offset + len(cdf) - 2]
         sym_range = (min(p[3] for p in parsed), max(p[3] + len(p[4]) - 2 for p in parsed), scale)
         bottom_level = parsed[0][0]
@@ -483,7 +511,7 @@ class GeoLosslessEntropyModel(nn.Module):
         pool: CoderPool = self._overlap_state(dev)['pool']
         c_ch = self.compressed_channels
         sym_t, progress = [], []
-        for _, rows, n_sym, sym_offset, sym_cdf, sym_payload, _, _ in parsed:
+        for _, rows, n_sym, sym_offset, sym_cdf, sym_payload, _, _, _ in parsed:
             t = torch.empty(n_sym * c_ch, dtype=torch.int32, pin_memory=True)
             progress.append(pool.table_decode(sym_payload, t.numel(), sym_cdf, sym_offset, t.numpy(), first_chunk=rows * c_ch))
             sym_t.append(t)
@@ -529,6 +557,22 @@ class GeoLosslessEntropyModel(nn.Module):
         if tm is not None:
             tm['dec_residual_decoded'] = time.perf_counter()
         occupancy = [p[6] for p in parsed]
+        interleaved = bool(parsed[0][8])
+        if any(bool(p[8]) != interleaved for p in parsed):
+            raise ValueError('the clouds of one traversal must share the format of their occupancy levels')
+        if interleaved:
+            # every block of every cloud and level to the device in ONE copy; block_at[c][level] = its offset there
+            block_at, total = [], 0
+            for blocks in occupancy:
+                block_at.append([])
+                for raw in blocks:
+                    block_at[-1].append(total)
+                    total += len(raw)
+            blocks_t = torch.zeros(total + 4, dtype=torch.uint8, pin_memory=True)
+            if total:
+                blocks_t[:total] = torch.frombuffer(bytearray(b''.join(raw for blocks in occupancy for raw in blocks)), dtype=torch.uint8)
+            blocks_d = blocks_t.to(dev, non_blocking=True)
+            level_no = 0
 
         for idx in range(len(self.residual_block) - 1, -1, -1):
             occ_net = self.hyper_decoder_coord[idx]
@@ -537,6 +581,30 @@ class GeoLosslessEntropyModel(nn.Module):
                 logits = occ_net(lower)
                 ta = time.perf_counter()
                 prob_d = ops.logit_to_prob16(logits.F.view(-1))
+                if interleaved:
+                    cand = [8 * e for e in (cm.batch_offsets(cur_map) if B > 1 else [0, cur_map.n])]
+                    # the headers are validated here, on the host, before the launch (ValueError); the kernel checks every descriptor again
+                    if any(not occupancy[c] for c in range(B)):
+                        raise ValueError('the bitstream holds fewer occupancy levels than the pyramid needs')
+                    table = np.concatenate([InterleavedBinaryCoder.chunk_table(occupancy[c].pop(0), cand[c + 1] - cand[c],
+                                                                               block_at[c][level_no], cand[c], c) for c in range(B)])
+                    level_no += 1
+                    chunks_d = torch.from_numpy(table).pin_memory().to(dev, non_blocking=True)
+                    mask, counts_d = ops.rans_binary_il_decode_dev(blocks_d, chunks_d, prob_d, B)
+                    *counts, bad = counts_d.tolist()                      # the level's one read-back: B counts and the status word
+                    if bad != 0:
+                        raise ValueError('corrupt occupancy block (status %d)' % bad)
+                    if tm is not None:
+                        tm['dec_wait'] += time.perf_counter() - ta
+                    gen_id = logits.coordinate_map_key.get_key()[1]
+                    cur_map = cm._refine(cur_map, mask, gen_id + 'pruned', count_hint=sum(counts), cloud_counts=counts if B > 1 else None)
+                    del logits
+                    fea_pred = self.hyper_decoder_fea[idx](lower, cur_map.key)
+                    if idx > self.skip_encoding_fea:
+                        lower = self._decode_residual(idx, residuals(counts), fea_pred, sym_range)
+                    else:
+                        lower = self.decoder_block[idx](fea_pred)
+                    continue
                 if self.device_decoder:
                     if B != 1:
                         raise NotImplementedError('the device-side occupancy decoder takes one cloud')

@@ -44,6 +44,7 @@ class PCC(nn.Module):
                                           cfg.skip_encoding_fea),
             hyper_decoder_coord=HyperDecoderGenUpsample(ch[1:], cfg.geo_lossl_if_sample, region, act),
             hyper_decoder_fea=HyperDecoderUpsample(ch[1:], ch[:-1], cfg.geo_lossl_if_sample, region, act))
+        self.em_lossless_based.occupancy_format = cfg.occupancy_stream_format
 
     def forward(self, pc_data: PCData):
         if self.training:

@@ -32,8 +32,14 @@ class ModelConfig:
     warmup_fea_loss_factor: float = 0.2
     warmup_color_loss_factor: float = 1.0
     linear_warmup: bool = False
+    # not a key of the reference's config: how the ENCODER writes the occupancy levels.  'reference' = the reference's single-state
+    # binary streams, byte-compatible; 'interleaved' = interleaved blocks coded on the device ("Interleaved occupancy
+    # blocks"), marked in the stream -- a decoder reads either, whatever this says.
+    occupancy_stream_format: str = 'reference'
 
     def __post_init__(self):
+        if self.occupancy_stream_format not in ('reference', 'interleaved'):
+            raise ValueError("occupancy_stream_format must be 'reference' or 'interleaved'")
         for f in fields(self):
             v = getattr(self, f.name)
             if isinstance(v, list):

@@ -36,8 +36,14 @@ class ModelConfig:
     # (include/fpcc_hip.h), so that a decoder with other summation-order rules refuses the stream instead of decoding garbage.
     # Default False = the reference's byte layout exactly.
     numerics_version_in_header: bool = False
+    # not a key of the reference's config either: how the ENCODER writes the occupancy levels.  'reference' = the reference's
+    # single-state binary streams, byte-compatible; 'interleaved' = interleaved blocks coded on the device (INTEGRATION.md,
+    # "Interleaved occupancy blocks"), marked in the stream -- a decoder reads either, whatever this says.
+    occupancy_stream_format: str = 'reference'
 
     def __post_init__(self):
+        if self.occupancy_stream_format not in ('reference', 'interleaved'):
+            raise ValueError("occupancy_stream_format must be 'reference' or 'interleaved'")
         for f in fields(self):
             v = getattr(self, f.name)
             if isinstance(v, list):

@@ -130,6 +130,8 @@ _SIGS = {
     'fpcc_logits_to_ranges': (_i32, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     'fpcc_rans_binary_decode_dev': (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     'fpcc_simple_dec_pop_dev': (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    'fpcc_rans_binary_il_encode_dev': (_i64, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'fpcc_rans_binary_il_decode_dev': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
     'fpcc_device_count': (_i32, []),
     'fpcc_clock_probe': (_i32, [_vp, _i32, _vp]),
     'fpcc_mlp_chain_f32': (_i32, [_vp, _vp]),
@@ -2034,3 +2036,57 @@ def simple_dec_pop_dev(state: torch.Tensor, stream: torch.Tensor, stream_len: in
     _ok(lib().fpcc_simple_dec_pop_dev(_dev(state, torch.int32, 'state'), _dev(stream, torch.uint8, 'stream'), int(stream_len),
                                       _dev(rows, torch.int16, 'rows', n == 0), n, width, sym.data_ptr(), n, children.data_ptr(), _stream()))
     return sym, children
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# interleaved binary rANS blocks (one wave per chunk; INTEGRATION.md, "Interleaved occupancy blocks")
+
+def rans_binary_il_encode_dev(bits: torch.Tensor, prob16: torch.Tensor, seg_edges: Sequence[int],
+                              ab: Optional[Tuple[int, int]] = None):
+    """bits uint8 [n], prob16 int16 [n] (uint16 bits) on the device; seg_edges: host list [n_seg + 1] of symbol offsets, one block per
+    segment [seg_edges[s], seg_edges[s + 1]); ab = (a, b) for every segment, None: the default policy per segment.
+    -> (out uint8 [worst case], meta int64 [n_seg + 1], offsets): block s is out[offsets[s]: offsets[s] + meta[s]], meta[n_seg] is the
+    status word (non-zero: a zero probability, the blocks are void).  Nothing is synchronised: `meta` is read after the caller's own
+    copy / synchronise."""
+    from .rans_coder import InterleavedBinaryCoder
+    edges = [int(e) for e in seg_edges]
+    n_seg = len(edges) - 1
+    n = bits.numel()
+    if n_seg < 1 or edges[0] < 0 or edges[-1] > n or any(b < a for a, b in zip(edges[:-1], edges[1:])) or prob16.numel() != n:
+        raise ValueError('seg_edges must rise inside [0, n], one probability per bit')
+    for a, b in [ab] if ab is not None else []:
+        if not (0 <= int(a) <= 6 and 4 <= int(b) <= 12):
+            raise ValueError('a in 0..6 and b in 4..12 expected')
+    abs_ = [ab if ab is not None else InterleavedBinaryCoder.policy(e1 - e0) for e0, e1 in zip(edges[:-1], edges[1:])]
+    dev = bits.device
+    table = torch.tensor(edges + [int(a) | int(b) << 8 for a, b in abs_], dtype=torch.int64, pin_memory=True)
+    offsets = torch.zeros(n_seg + 1, dtype=torch.int64)
+    L = lib()
+    need = _ok(L.fpcc_rans_binary_il_encode_dev(None, None, table.data_ptr(), None, n_seg, None, 0, None, None, offsets.data_ptr(), None, 0, None))
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+    offsets = offsets.tolist()
+    out = torch.empty(max(offsets[-1], 16), dtype=torch.uint8, device=dev)
+    meta = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    table_d = table.to(dev, non_blocking=True)
+    _ok(L.fpcc_rans_binary_il_encode_dev(_dev(bits, torch.uint8, 'bits', n == 0), _dev(prob16, torch.int16, 'prob16', n == 0), table.data_ptr(),
+                                         table_d.data_ptr(), n_seg, out.data_ptr(), out.numel(), meta.data_ptr(), meta.data_ptr() + 8 * n_seg,
+                                         None, ws.data_ptr(), int(need), _stream()))
+    return out, meta, offsets
+
+
+def rans_binary_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, prob16: torch.Tensor, n_seg: int):
+    """blocks uint8 [bytes] and chunks int64 [n_chunks, 6] on the device (the descriptors rans_coder.InterleavedBinaryCoder.chunk_table
+    builds from validated headers), prob16 int16 [n] -> (bits uint8 [n], counts int32 [n_seg + 1]: ones per segment, then the sticky
+    status word, 0 = fine), all on the device; nothing is synchronised"""
+    n = prob16.numel()
+    dev = prob16.device
+    if chunks.dim() != 2 or chunks.shape[1] != 6 or n_seg < 1:
+        raise ValueError('chunks must be [n_chunks, 6], n_seg >= 1')
+    bits = torch.empty(n, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(n_seg + 1, dtype=torch.int32, device=dev)
+    n_chunks = chunks.shape[0]
+    _ok(lib().fpcc_rans_binary_il_decode_dev(_dev(blocks, torch.uint8, 'blocks', n_chunks == 0), blocks.numel() if blocks is not None else 0,
+                                             _dev(chunks, torch.int64, 'chunks', n_chunks == 0), n_chunks,
+                                             _dev(prob16, torch.int16, 'prob16', n_chunks == 0), n, bits.data_ptr(), counts.data_ptr(), int(n_seg),
+                                             counts.data_ptr() + 4 * int(n_seg), _stream()))
+    return bits, counts

@@ -8,7 +8,7 @@
 backed by libfpcc_host.so through its C ABI (include/fpcc_host.h).  Argument meaning follows the reference; where the
 reference aborts through a C assert, these raise RuntimeError/ValueError instead.
 """
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -149,6 +149,97 @@ class BinaryRansCoder:
             row = symbol_array[b].view(np.uint8)
             host_check(host().fpcc_rans_binary_decode(_p(data), data.size, _p(prob[b]), row.size, _p(row)))
         return 0
+
+
+class InterleavedBinaryCoder:
+    """The binary coder with 2^a interleaved states: one block per call ("Interleaved occupancy blocks").  The host
+    pair of libfpcc_host; the device pair is hipops.rans_binary_il_encode_dev / rans_binary_il_decode_dev -- same bytes."""
+    TAG = 0xA0
+
+    @staticmethod
+    def policy(n: int) -> Tuple[int, int]:
+        """(a, b) the encoders choose for n symbols: 1024 symbols per lane and chunk; 64 lanes from 16384 symbols on, below that the
+        largest power of two that leaves a lane 256 symbols"""
+        if n >= 16384:
+            return 6, 10
+        return max(1, n // 256).bit_length() - 1, 10
+
+    @staticmethod
+    def n_chunks(n: int, a: int, b: int) -> int:
+        return (n + (1 << (a + b)) - 1) >> (a + b)
+
+    @classmethod
+    def worst_case_bytes(cls, n: int, a: int, b: int) -> int:
+        """header + lengths + per chunk the initial states and two bytes per symbol"""
+        k = cls.n_chunks(n, a, b)
+        return 6 + 4 * k + 4 * (1 << a) * k + 2 * n
+
+    @classmethod
+    def parse_header(cls, block, n: int) -> Tuple[int, int, List[int]]:
+        """(a, b, chunk payload lengths) of a block that codes n symbols; ValueError for anything a decoder must not be started on"""
+        block = memoryview(block)
+        if len(block) < 6:
+            raise ValueError('interleaved block: shorter than its header')
+        if block[0] & 0xF8 != cls.TAG:
+            raise ValueError('interleaved block: wrong tag byte')
+        a, b = block[0] & 7, block[1]
+        if a > 6 or not 4 <= b <= 12:
+            raise ValueError('interleaved block: lanes = 2^a with a in 0..6 and symbols per lane = 2^b with b in 4..12')
+        if int.from_bytes(block[2:6], 'little') != n:
+            raise ValueError('interleaved block: codes another number of symbols than the level has candidates')
+        k = cls.n_chunks(n, a, b)
+        if len(block) < 6 + 4 * k:
+            raise ValueError('interleaved block: shorter than its table of chunk lengths')
+        lens = np.frombuffer(block[6:6 + 4 * k], dtype='<u4').astype(np.int64).tolist()
+        if any(v < 4 << a for v in lens):
+            raise ValueError('interleaved block: a chunk shorter than its initial states')
+        if sum(lens) != len(block) - 6 - 4 * k:
+            raise ValueError('interleaved block: chunk lengths do not sum to the payload')
+        return a, b, lens
+
+    @classmethod
+    def chunk_table(cls, block, n: int, block_at: int, sym0: int, seg: int) -> np.ndarray:
+        """int64 [K, 6] descriptors of a VALIDATED block for fpcc_rans_binary_il_decode_dev: the block lies at byte `block_at` of the
+        device buffer and codes symbols [sym0, sym0 + n) of segment `seg`"""
+        a, b, lens = cls.parse_header(block, n)
+        k = len(lens)
+        out = np.empty((k, 6), dtype=np.int64)
+        lens = np.asarray(lens, dtype=np.int64)
+        out[:, 0] = block_at + 6 + 4 * k + np.cumsum(lens) - lens
+        out[:, 1] = lens
+        out[:, 2] = sym0 + (np.arange(k, dtype=np.int64) << (a + b))
+        out[:, 3] = np.minimum(1 << (a + b), n - (np.arange(k, dtype=np.int64) << (a + b)))
+        out[:, 4] = seg
+        out[:, 5] = a
+        return out
+
+    def encode(self, symbol_array: np.ndarray, prob_array: np.ndarray, a: Optional[int] = None, b: Optional[int] = None) -> bytes:
+        bits = np.ascontiguousarray(np.asarray(symbol_array).reshape(-1) != 0).view(np.uint8)
+        prob = np.ascontiguousarray(np.asarray(prob_array).reshape(-1), dtype=np.uint16)
+        if bits.shape != prob.shape:
+            raise ValueError('one probability per symbol expected')
+        n = bits.size
+        pa, pb = self.policy(n)
+        a, b = pa if a is None else int(a), pb if b is None else int(b)
+        if not (0 <= a <= 6 and 4 <= b <= 12):
+            raise ValueError('a in 0..6 and b in 4..12 expected')
+        if n and int(prob.min()) == 0:
+            raise ValueError('a zero probability cannot be coded')
+        cap = self.worst_case_bytes(n, a, b)
+        buf = np.empty(cap, dtype=np.uint8)
+        got = host_check(host().fpcc_rans_binary_il_encode(_p(bits), _p(prob), n, a, b, _p(buf), cap))
+        return buf[:got].tobytes()
+
+    def decode(self, block: bytes, prob_array: np.ndarray) -> np.ndarray:
+        """-> uint8 [n] bits"""
+        prob = np.ascontiguousarray(np.asarray(prob_array).reshape(-1), dtype=np.uint16)
+        self.parse_header(block, prob.size)
+        data = np.frombuffer(block, dtype=np.uint8)
+        out = np.empty(prob.size, dtype=np.uint8)
+        code = host().fpcc_rans_binary_il_decode(_p(data), data.size, _p(prob), prob.size, _p(out))
+        if code < 0:
+            raise ValueError('interleaved block: ' + host().fpcc_host_strerror(code).decode())
+        return out
 
 
 class RansEncoder:

@@ -910,6 +910,30 @@ int fpcc_simple_dec_pop_dev(int32_t *state, const uint8_t *stream, int64_t strea
                             int64_t n_rows, int64_t width, uint16_t *symbols_out, int64_t n, int32_t *children_out,
                             void *hip_stream);
 
+/* Interleaved binary rANS blocks (rans_il.hip): the opt-in occupancy block format of INTEGRATION.md ("Interleaved occupancy blocks"),
+ * byte for byte what fpcc_rans_binary_il_encode / _decode of libfpcc_host write and read.  One wave codes one chunk; the chunks of all
+ * segments (the clouds of one level) are one launch.  Neither call synchronises or reads anything back.
+ *
+ * Segment table, int64 [2 n_seg + 1], given twice -- seg_host (host memory: sizes and launch geometry) and seg (the same words on the
+ * device: the kernels) --: [0 .. n_seg] the segments' symbol offsets into bits / prob1 (not decreasing), then per segment a | b << 8
+ * (lanes = 2^a, a in 0..6; symbols per lane and chunk = 2^b, b in 4..12).  A chunk never spans a segment.
+ * encode: block s is written contiguously at out + block_off_host[s] (the worst-case offsets, n_seg + 1 of them, filled on every call that
+ *   has the pointer, the size query included; out_bytes >= block_off_host[n_seg]) and len_out[s] (device int64) receives its length.
+ *   *status (device, zeroed by the caller) gets bit 0 when a probability is zero: the blocks are then void and must be discarded.
+ *   ws == NULL returns the workspace size in bytes (a function of seg_host alone). */
+int64_t fpcc_rans_binary_il_encode_dev(const uint8_t *bits, const uint16_t *prob1, const int64_t *seg_host, const int64_t *seg,
+                                       int32_t n_seg, uint8_t *out, int64_t out_bytes, int64_t *len_out, int32_t *status,
+                                       int64_t *block_off_host, void *ws, int64_t ws_bytes, void *stream);
+/* decode: blocks [blocks_bytes] holds the blocks of a level (anywhere in it); chunks int64 [n_chunks][6] = {byte offset of the chunk's
+ *   payload in blocks, payload length, first symbol, symbols, segment, a}, built by the HOST from headers it has validated (tag, a, b,
+ *   n, lengths >= 4 lanes that sum to the block).  The kernel checks every descriptor against blocks_bytes, n and n_seg before it
+ *   forms an address; a byte past a chunk's payload reads as zero.  bits_out uint8 [n]; ones_out int32 [n_seg] (zeroed by the caller)
+ *   gets the number of ones per segment; *status (zeroed by the caller) is sticky: bit 0 an initial state below 2^23, bit 2 a chunk
+ *   read past its payload, bit 3 a descriptor outside the buffers (that chunk is skipped). */
+int fpcc_rans_binary_il_decode_dev(const uint8_t *blocks, int64_t blocks_bytes, const int64_t *chunks, int64_t n_chunks,
+                                   const uint16_t *prob1, int64_t n, uint8_t *bits_out, int32_t *ones_out, int32_t n_seg,
+                                   int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Mixed-precision TRAINING: bfloat16 operands, fp32 accumulation (conv_bf16.hip).  Never used by inference.       */
 /* ------------------------------------------------------------------------------------------------------------ */

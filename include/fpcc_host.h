@@ -56,6 +56,16 @@ int64_t fpcc_rans_binary_encode(const uint8_t *bits, const uint16_t *prob1, int6
 int64_t fpcc_rans_binary_decode(const uint8_t *stream, int64_t stream_len, const uint16_t *prob1, int64_t n,
                                 uint8_t *bits_out);
 
+/* The same binary coder with 2^a interleaved states: the opt-in occupancy block format of INTEGRATION.md ("Interleaved occupancy
+ * blocks"; no counterpart in the reference).  Host statement of the format and oracle of the device pair fpcc_rans_binary_il_*_dev.
+ * encode: a in 0..6 and b in 4..12, or -1 for the default policy (written into the header).  Writes the block at the START of
+ *         out[0..cap) and returns its length; a zero probability is FPCC_HOST_E_ARG, a block that does not fit FPCC_HOST_E_BUFFER.
+ * decode: `n` is the number of symbols the caller expects (the length of prob1).  The header is validated before a payload byte is
+ *         read -- tag, a, b, n, every chunk length >= 4 * lanes, lengths summing to the rest of the block -- and so is every initial
+ *         state (>= 2^23): FPCC_HOST_E_ARG otherwise.  Bytes past a chunk's payload read as zero. */
+int64_t fpcc_rans_binary_il_encode(const uint8_t *bits, const uint16_t *prob1, int64_t n, int a, int b, uint8_t *out, int64_t cap);
+int64_t fpcc_rans_binary_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *prob1, int64_t n, uint8_t *bits_out);
+
 /* Several independent binary streams at once, one host thread each (the reference's OpenMP-over-batch loop,
  * rans_wrapper.cpp:340-341, used here across the occupancy levels of one frame).  Stream s covers
  * bits[start[s] .. start[s+1]).  Its bytes are written at the END of out + s*cap_each .. +cap_each; len_out[s] gets the
