@@ -1343,6 +1343,8 @@ def epilogue_bwd(y: torch.Tensor, dy: torch.Tensor, act: int, slope: Optional[to
 def deep_factorized_bits(y: torch.Tensor, weights, biases, factors, half_width: float, want_dy: bool = True):
     """y [n, c] fp32; parameters as stored by NoisyDeepFactorizedEntropyModel (filters 1-3-3-3-3-1).
     -> (out [c, 59]: parameter gradients of sum(logp) then sum(logp), dy [n, c] | None)"""
+    if y.dim() != 2 or y.dtype != torch.float32:
+        raise ValueError(f'y must be a 2-D float32 tensor, got {tuple(y.shape)} {y.dtype}')
     py, c, ldy = _rows2d(y, 'y')
     n = y.shape[0]
     if len(weights) != 5 or len(biases) != 5 or len(factors) != 4:
@@ -1351,6 +1353,13 @@ def deep_factorized_bits(y: torch.Tensor, weights, biases, factors, half_width: 
     for t, sh in zip(weights, shapes):
         if tuple(t.shape) != sh:
             raise ValueError(f'weight of shape {tuple(t.shape)}, expected {sh}')
+    # the kernel reads c * f_out biases and factors per layer, whatever the tensors hold
+    for what, ts in (('bias', biases), ('factor', factors)):
+        for t, sh in zip(ts, shapes):
+            if tuple(t.shape) not in ((c, sh[1], 1), (c, sh[1])):
+                raise ValueError(f'{what} of shape {tuple(t.shape)}, expected {(c, sh[1], 1)}')
+    if not half_width > 0:
+        raise ValueError(f'half_width must be positive, got {half_width}')
     ptr = lambda ts: (C.c_void_p * len(ts))(*[_dev(t.detach(), torch.float32, 'parameter') for t in ts])
     out = torch.empty((c, 59), dtype=torch.float32, device=y.device)
     dy = torch.empty((n, c), dtype=torch.float32, device=y.device) if want_dy else None
@@ -1366,8 +1375,12 @@ def noisy_normal_bits(y: torch.Tensor, index: torch.Tensor, log_scale_offset: fl
                       half_width: float = 0.5):
     """-> (sum of log-probabilities (0-dim), d/dy [n], d/dindex [n]) of y under N(0, exp(offset + factor * index)) + U(-h, h)"""
     n = y.numel()
-    if index.numel() != n:
-        raise ValueError('one index per value')
+    if index.shape != y.shape:
+        raise ValueError(f'one index per value: index {tuple(index.shape)}, y {tuple(y.shape)}')
+    if y.dtype != torch.float32:
+        raise ValueError(f'y must be float32, got {y.dtype}')
+    if not half_width > 0:
+        raise ValueError(f'half_width must be positive, got {half_width}')
     index = index.to(torch.float32)
     py, pi = _dev(y, torch.float32, 'y', n == 0), _dev(index, torch.float32, 'index', n == 0)
     dy = torch.empty(n, dtype=torch.float32, device=y.device)
