@@ -524,6 +524,10 @@ __global__ __launch_bounds__(256) void k_epilogue_bwd(const float *__restrict__ 
 // channels is 32 lanes, a workgroup covers 8 rows per pass and keeps four passes in flight.  The scalar kernel above moved 1.4 TB/s
 // over the training step's layers (4-byte accesses, one row per thread and pass); the sums per row block are formed in a fixed
 // order here too (per lane over its rows ascending, then over the row groups ascending).
+// kVec false: the same lanes, rows and sums on 4-byte accesses, for a c % 4 == 0 whose pointers or row strides are not multiples of
+// 16 bytes (dy a column slice at an odd offset of a concatenation's gradient) -- so that dbias and dslope of a width have ONE
+// association, whatever the layout of the operands.
+template <bool kVec>
 __global__ __launch_bounds__(256) void k_epilogue_bwd_v4(const float *__restrict__ y, int ldy, const float *__restrict__ dy, int lddy,
                                                          int64_t n, int c, int cpad4, int act, const float *__restrict__ slope,
                                                          float *__restrict__ g, int ldg, float *__restrict__ partial) {
@@ -541,10 +545,16 @@ __global__ __launch_bounds__(256) void k_epilogue_bwd_v4(const float *__restrict
         if (cc < c) {
 #pragma unroll 4
             for (int64_t r = r0 + grp; r < r1; r += groups) {
-                const float4 yv = *reinterpret_cast<const float4 *>(y + r * ldy + cc);
-                const float4 d = *reinterpret_cast<const float4 *>(dy + r * lddy + cc);
-                const float ys[4] = {yv.x, yv.y, yv.z, yv.w}, ds[4] = {d.x, d.y, d.z, d.w};
-                float gv[4];
+                float ys[4], ds[4], gv[4];
+                if constexpr (kVec) {
+                    const float4 yv = *reinterpret_cast<const float4 *>(y + r * ldy + cc);
+                    const float4 d = *reinterpret_cast<const float4 *>(dy + r * lddy + cc);
+                    ys[0] = yv.x, ys[1] = yv.y, ys[2] = yv.z, ys[3] = yv.w;
+                    ds[0] = d.x, ds[1] = d.y, ds[2] = d.z, ds[3] = d.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ys[j] = y[r * ldy + cc + j], ds[j] = dy[r * lddy + cc + j];
+                }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     gv[j] = ds[j];
@@ -554,7 +564,12 @@ __global__ __launch_bounds__(256) void k_epilogue_bwd_v4(const float *__restrict
                     }
                     sg[j] += gv[j];
                 }
-                *reinterpret_cast<float4 *>(g + r * ldg + cc) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+                if constexpr (kVec) {
+                    *reinterpret_cast<float4 *>(g + r * ldg + cc) = make_float4(gv[0], gv[1], gv[2], gv[3]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) g[r * ldg + cc + j] = gv[j];
+                }
             }
         }
 #pragma unroll
@@ -619,13 +634,18 @@ extern "C" int fpcc_epilogue_bwd_f32(const float *y, int ldy, const float *dy, i
     if (!y || !dy || !g) return fail_arg("epilogue_bwd: null pointer");
     const int64_t blocks = (n + kEpiRows - 1) / kEpiRows;
     if (!ws || ws_bytes < blocks * (int64_t)(c + 1) * 4) return fail_arg("epilogue_bwd: workspace of fpcc_epilogue_bwd_ws_bytes() bytes required");
-    const bool vec4 = c % 4 == 0 && ldy % 4 == 0 && lddy % 4 == 0 && ldg % 4 == 0 &&
-                      ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
-    if (vec4) {
+    // the kernel, hence the association of dbias and dslope, is chosen by c alone; alignment only picks the width of the accesses
+    const bool aligned = ldy % 4 == 0 && lddy % 4 == 0 && ldg % 4 == 0 &&
+                         ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
+    if (c % 4 == 0) {
         int cpad4 = 1;
         while (cpad4 * 4 < c && cpad4 < 256) cpad4 <<= 1;
-        hipLaunchKernelGGL(k_epilogue_bwd_v4, dim3((unsigned)blocks), dim3(256), 0, s, y, ldy, dy, lddy, n, c, cpad4, act, slope, g, ldg,
-                           static_cast<float *>(ws));
+        if (aligned)
+            hipLaunchKernelGGL(k_epilogue_bwd_v4<true>, dim3((unsigned)blocks), dim3(256), 0, s, y, ldy, dy, lddy, n, c, cpad4, act, slope, g,
+                               ldg, static_cast<float *>(ws));
+        else
+            hipLaunchKernelGGL(k_epilogue_bwd_v4<false>, dim3((unsigned)blocks), dim3(256), 0, s, y, ldy, dy, lddy, n, c, cpad4, act, slope, g,
+                               ldg, static_cast<float *>(ws));
     } else {
         int cpad = 1;
         while (cpad < c && cpad < 256) cpad <<= 1;

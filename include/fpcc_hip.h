@@ -479,7 +479,8 @@ int fpcc_transpose_weights_f32(const float *w, int n_offsets, int c_in, int c_ou
  *     g = dy * act'(pre),   dbias[c] = sum_rows g[., c] (NULL: skipped),   dslope[0] = sum dy * pre over pre < 0 (NULL: skipped).
  * g feeds the input / weight gradients above.  Replaces the bias-add and MinkowskiPReLU autograd nodes of
  * lib/minkowski_sparse_conv_layers.py:85-91.  ws: fpcc_epilogue_bwd_ws_bytes() bytes of per-row-block partial sums,
- * reduced in ascending block order (reproducible).  g may alias dy. */
+ * reduced in ascending block order (reproducible): the association of dbias and dslope is a function of (n, c) alone -- row
+ * strides and alignment of y / dy / g only pick the width of the memory accesses, never a bit.  g may alias dy. */
 int64_t fpcc_epilogue_bwd_ws_bytes(int64_t n, int c);
 int fpcc_epilogue_bwd_f32(const float *y, int ldy, const float *dy, int lddy, int64_t n, int c, int act, const float *slope,
                           float *g, int ldg, float *dbias, float *dslope, void *ws, int64_t ws_bytes, void *stream);
