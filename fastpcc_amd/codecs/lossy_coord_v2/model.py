@@ -27,6 +27,9 @@ from .layers import Decoder, DecoderGeoLossl, Encoder, EncoderGeoLossl, HyperDec
 from .model_config import ModelConfig
 
 
+BF16_MARK = 0x80       # first header byte (numerics_version_in_header): set when the stream was written with inference_dtype = 'bfloat16'
+
+
 class PCC(nn.Module):
 
     @staticmethod
@@ -58,6 +61,21 @@ class PCC(nn.Module):
             hyper_decoder_coord=HyperDecoderGenUpsample(ch[1:], cfg.geo_lossl_if_sample, region, act),
             hyper_decoder_fea=HyperDecoderUpsample(ch[1:], ch[:-1], cfg.geo_lossl_if_sample, region, act))
         self.em_lossless_based.occupancy_format = cfg.occupancy_stream_format
+        if cfg.inference_dtype == 'bfloat16':
+            ME.mark_bf16_producers(self)
+
+    def set_inference_dtype(self, name: str) -> None:
+        """switch a built model between '' (fp32) and 'bfloat16' inference: what the `inference_dtype` key does at construction, for a
+        caller that only holds the model (fastpcc_amd.evaluate).  Validated by the config class ('float16' is refused by name)."""
+        import dataclasses
+        self.cfg = dataclasses.replace(self.cfg, inference_dtype=name)
+        if name == 'bfloat16':
+            ME.mark_bf16_producers(self)
+
+    def _inference_context(self):
+        """what compress / decompress run the networks in: cfg.inference_dtype = 'bfloat16' opens ME.conv_inference_dtype, '' the fp32
+        path explicitly (a default model called from inside somebody's bf16 context still writes fp32 streams)"""
+        return ME.conv_inference_dtype(torch.bfloat16 if self.cfg.inference_dtype == 'bfloat16' else None)
 
     # ---------------------------------------------------------------------------------------------------------------
     def forward(self, pc_data: PCData):
@@ -121,12 +139,18 @@ class PCC(nn.Module):
             raise RuntimeError('compress() runs on the GPU; move the coordinates there first')
         coord_offset = batched_coord.amin(0)[1:]        # reduce the contiguous [n, 4] tensor, then drop the batch column
         sparse_pc = self.get_sparse_pc((batched_coord - F.pad(coord_offset, (1, 0))).contiguous())
-        feature, points_num_list = self.encoder(sparse_pc)
-        em_bytes = self.em_lossless_based.compress(feature, 1)
+        with self._inference_context():
+            feature, points_num_list = self.encoder(sparse_pc)
+            em_bytes = self.em_lossless_based.compress(feature, 1)
         return self._header(coord_offset.tolist(), None if points_num_list is None else [counts[0] for counts in points_num_list]) + em_bytes
 
     def _header(self, coord_offset: List[int], counts: Optional[List[int]]) -> bytes:
-        head = bytes([hipops.numerics_version()]) if self.cfg.numerics_version_in_header else b''
+        head = b''
+        if self.cfg.numerics_version_in_header:
+            head = bytes([hipops.numerics_version()])
+            if self.cfg.inference_dtype == 'bfloat16':
+                # the marker of a bf16 stream: the top bit of the numerics byte, then the version of the eligible-layer set
+                head = bytes([hipops.numerics_version() | BF16_MARK, hipops.FPCC_BF16_PROFILE_VERSION])
         head += b''.join(int(v).to_bytes(2, 'little', signed=False) for v in coord_offset)
         if self.cfg.adaptive_pruning:
             head += b''.join(int(n).to_bytes(3, 'little', signed=False) for n in counts)
@@ -149,8 +173,9 @@ class PCC(nn.Module):
         shift = offsets.clone()
         shift[:, 0] = -torch.arange(B, device=shift.device, dtype=shift.dtype)          # cloud b becomes sample b of the batch
         sparse_pc = self.get_sparse_pc(torch.cat([c - shift[b] for b, c in enumerate(clouds)]), clouds=B)
-        feature, points_num_list = self.encoder(sparse_pc)
-        em_bytes = self.em_lossless_based.compress_clouds(feature, B)
+        with self._inference_context():
+            feature, points_num_list = self.encoder(sparse_pc)
+            em_bytes = self.em_lossless_based.compress_clouds(feature, B)
         offsets = offsets[:, 1:].tolist()
         return [self._header(offsets[b], None if points_num_list is None else [counts[b] for counts in points_num_list]) + em_bytes[b]
                 for b in range(B)]
@@ -173,8 +198,9 @@ class PCC(nn.Module):
         points_num_list = None
         if self.cfg.adaptive_pruning:
             points_num_list = [[targets[b][s][0] for b in range(B)] for s in range(len(targets[0]))]
-        fea_recon = self.em_lossless_based.decompress_clouds(payloads, self.set_global_cm(B))
-        return self.decoder(fea_recon, points_num_list, offset_t)
+        with self._inference_context():
+            fea_recon = self.em_lossless_based.decompress_clouds(payloads, self.set_global_cm(B))
+            return self.decoder(fea_recon, points_num_list, offset_t)
 
     # partitions of one list are coded together up to this many voxels per traversal (activations of every level stay resident)
     MANY_MAX_VOXELS = 6_000_000
@@ -204,6 +230,16 @@ class PCC(nn.Module):
         with io.BytesIO(compressed_bytes) as bs:
             if self.cfg.numerics_version_in_header:
                 written_by = bs.read(1)[0]
+                bf16 = self.cfg.inference_dtype == 'bfloat16'
+                if bool(written_by & BF16_MARK) != bf16:
+                    raise ValueError('stream written with bfloat16 inference, this model decodes fp32 streams' if not bf16 else
+                                     'stream written with fp32 inference, this model (inference_dtype = bfloat16) decodes bfloat16 streams')
+                written_by &= BF16_MARK - 1
+                if bf16:
+                    profile = bs.read(1)[0]
+                    if profile != hipops.FPCC_BF16_PROFILE_VERSION:
+                        raise ValueError(f'stream written with bfloat16 profile version {profile}, this build decodes version '
+                                         f'{hipops.FPCC_BF16_PROFILE_VERSION} (the set of bf16 layers is part of the format)')
                 if written_by != hipops.numerics_version():
                     raise ValueError(f'stream written with numerics version {written_by}, this build decodes version '
                                      f'{hipops.numerics_version()} (the fp32 summation orders are part of the format)')
@@ -221,8 +257,9 @@ class PCC(nn.Module):
         coord_offset, points_num_list, em_bytes = self._parse_header(compressed_bytes)
         # made before anything is queued: a host-to-device copy from pageable memory waits for the stream
         offset = torch.tensor(coord_offset, dtype=torch.int32, device=dev)
-        fea_recon = self.em_lossless_based.decompress(em_bytes, self.set_global_cm())
-        return self.decoder(fea_recon, points_num_list, offset)
+        with self._inference_context():
+            fea_recon = self.em_lossless_based.decompress(em_bytes, self.set_global_cm())
+            return self.decoder(fea_recon, points_num_list, offset)
 
     def decompress_partitions(self, concat_bytes: bytes) -> torch.Tensor:
         streams = []

@@ -40,8 +40,18 @@ class ModelConfig:
     # single-state binary streams, byte-compatible; 'interleaved' = interleaved blocks coded on the device (INTEGRATION.md,
     # "Interleaved occupancy blocks"), marked in the stream -- a decoder reads either, whatever this says.
     occupancy_stream_format: str = 'reference'
+    # not a key of the reference's config either: '' = fp32 inference, the reference's bytes; 'bfloat16' = the eligible convolution layers
+    # (hipops.bf16_inference_eligible, versioned as hipops.FPCC_BF16_PROFILE_VERSION) run with bf16 operands on the bf16 matrix pipe in
+    # compress and decompress alike.  Such a stream decodes only with a model in the same mode ("Stream compatibility");
+    # with numerics_version_in_header it says so in its first two bytes.
+    inference_dtype: str = ''
 
     def __post_init__(self):
+        if self.inference_dtype == 'float16':
+            raise ValueError("inference_dtype 'float16' is not offered: use 'bfloat16' (the fp32 range, and the rate of the same matrix "
+                             "instructions on gfx950)")
+        if self.inference_dtype not in ('', 'bfloat16'):
+            raise ValueError("inference_dtype must be '' (fp32) or 'bfloat16'")
         if self.occupancy_stream_format not in ('reference', 'interleaved'):
             raise ValueError("occupancy_stream_format must be 'reference' or 'interleaved'")
         for f in fields(self):

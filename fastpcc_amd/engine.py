@@ -88,6 +88,34 @@ def global_coordinate_manager() -> Optional['CoordinateManager']:
     return getattr(_tls, 'cm', None)
 
 
+class conv_inference_dtype:
+    """Context of the CALLING thread: with torch.bfloat16, the fused inference path of the convolution modules (gradients disabled)
+    sends every layer of hipops.bf16_inference_eligible to fpcc_conv_bf16_fused -- bf16 operands on the bf16 matrix pipe, fp32
+    accumulation, fp32 results; every other layer, and everything outside the context, keeps its fp32 evaluation and its bits.  Which
+    layers are sent is a function of their kind and channel counts alone (part of the stream format of a codec run in this mode).
+    Separate from conv_autocast (training), which inference ignores.  None / torch.float32: the fp32 path.  Re-entrant."""
+
+    def __init__(self, dtype=torch.bfloat16):
+        if dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError(f'conv_inference_dtype takes torch.bfloat16 or torch.float32, not {dtype} '
+                             '(float16 is not offered: gfx950 has no advantage for it over bfloat16 and its range is too small)')
+        self.dtype = None if dtype == torch.float32 else dtype
+
+    def __enter__(self):
+        self._prev = getattr(_tls, 'infer_dtype', None)
+        _tls.infer_dtype = self.dtype
+        return self
+
+    def __exit__(self, *exc):
+        _tls.infer_dtype = self._prev
+        return False
+
+
+def inference_dtype():
+    """torch.bfloat16 inside conv_inference_dtype(torch.bfloat16) on this thread, else None"""
+    return getattr(_tls, 'infer_dtype', None)
+
+
 def _as_stride(s) -> Tuple[int, int, int]:
     if isinstance(s, int):
         return (s, s, s)
@@ -429,7 +457,7 @@ class CoordinateManager:
                                                  masks=m.mask27 if m.nbr27_rows is not None else None, unit=unit)
         return m.row_order
 
-    def _k2_order(self, src: _Map):
+    def _k2_order(self, src: _Map, want_table: bool = True):
         """(row order, table) of the stride-2 2x2x2 convolution from `src` onto its parent on the MFMA path.  A parent has ~3.7 of its 8
         children on a surface, yet in Morton order nearly every 32-row block of parents has all 8 octants between its rows, so the
         kernel executed all 8 offsets for every block (0.33 of the matrix peak on the large maps, rounds 2-5).  Grouping the parents by
@@ -441,9 +469,12 @@ class CoordinateManager:
             src.k2_order = None
             if self.NBR_ROWS and m > self.ROW_ORDER_MIN_ROWS and os.environ.get('FPCC_K2_ROW_ORDER', '1') != '0':
                 src.k2_order = ops.conv_row_order(src.child_row, 8, 1, 8, m, self.ROW_ORDER_WINDOW_LOG2)
-                src.k2_pos = ops.gather_table_rows(src.child_row, src.k2_order)
         if src.k2_order is None:
             return None, src.child_row
+        if not want_table:             # a caller that indexes the table by output row (the bf16 entry) needs the order alone
+            return src.k2_order, None
+        if src.k2_pos is None:
+            src.k2_pos = ops.gather_table_rows(src.child_row, src.k2_order)
         return src.k2_order, src.k2_pos
 
     K2T_WINDOW_LOG2 = ops.K2S2T_WINDOW_LOG2       # rows per window of the transposed layers' octant order
@@ -592,6 +623,10 @@ class SparseTensor:
             raise ValueError('coordinates or coordinate_map_key required')
         self.coordinate_map_key = coordinate_map_key
         self._parts = features if isinstance(features, tuple) else (features,)
+        # bf16 companions of the parts, used only inside conv_inference_dtype(torch.bfloat16): per part None or (tensor, raw stream it was
+        # made on).  A cache of part.bfloat16(), never a definition: written by a producing bf16 layer that was asked to, else cast once
+        # on first use (bf16_parts)
+        self._bf16: Optional[list] = None
         n_rows = coordinate_manager._map(coordinate_map_key).n
         for f in self._parts:
             if f.shape[0] != n_rows:
@@ -602,11 +637,39 @@ class SparseTensor:
     def F(self) -> torch.Tensor:
         if len(self._parts) > 1:
             self._parts = (torch.cat(self._parts, dim=1),)
+            self._bf16 = None
         return self._parts[0]
 
     @property
     def parts(self) -> Tuple[torch.Tensor, ...]:
         return self._parts
+
+    def bf16_parts(self) -> Tuple[torch.Tensor, ...]:
+        """the parts as bfloat16 rows (round to nearest even): the companion a producing layer wrote, else ONE fpcc_cast_f32_bf16 per part,
+        kept -- a tensor read by several bf16 layers (`lower` of a pyramid level: both hyper decoders) is cast once.  A companion made on
+        another stream than the caller's (the occupancy predictors may run on a side stream) is waited for.  The cache assumes what the
+        engine's own layers guarantee: the features of a tensor that a convolution has read are not written in place afterwards."""
+        if self._bf16 is None:
+            self._bf16 = [None] * len(self._parts)
+        cur = ops._stream()
+        out = []
+        for i, p in enumerate(self._parts):
+            ent = self._bf16[i]
+            if ent is None:
+                if p.stride(1) != 1 or p.stride(0) % 4 or p.data_ptr() % 16:
+                    p = p.contiguous()                   # (the cast reads whole 16-byte pieces)
+                ent = self._bf16[i] = (ops.cast_bf16(p), cur)
+            elif ent[1] != cur:
+                here = torch.cuda.current_stream()
+                here.wait_stream(torch.cuda.ExternalStream(ent[1]) if ent[1] else torch.cuda.default_stream())
+                ent[0].record_stream(here)
+            out.append(ent[0])
+        return tuple(out)
+
+    @property
+    def has_bf16(self) -> bool:
+        """whether any part carries a bf16 companion (tests)"""
+        return self._bf16 is not None and any(e is not None for e in self._bf16)
 
     @property
     def C(self) -> torch.Tensor:
@@ -668,14 +731,19 @@ def cat(*tensors) -> SparseTensor:
     if len(tensors) == 1 and isinstance(tensors[0], (tuple, list)):
         tensors = tuple(tensors[0])
     key, cm = tensors[0].coordinate_map_key, tensors[0].coordinate_manager
-    parts = []
+    parts, bf16 = [], []
     for t in tensors:
         if t.coordinate_manager is not cm or cm._map(t.coordinate_map_key) is not cm._map(key):
             raise ValueError('cat needs tensors on the same coordinate map')
         parts.extend(t.parts)
+        bf16.extend(t._bf16 if t._bf16 is not None else [None] * len(t.parts))
     if len(parts) > 2:
         parts = [torch.cat(parts[:-1], dim=1), parts[-1]]
-    return SparseTensor(tuple(parts), coordinate_map_key=key, coordinate_manager=cm)
+        bf16 = [None, bf16[-1]]
+    out = SparseTensor(tuple(parts), coordinate_map_key=key, coordinate_manager=cm)
+    if any(e is not None for e in bf16):           # (only ever inside conv_inference_dtype: the parts keep their bf16 companions)
+        out._bf16 = bf16
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -802,6 +870,7 @@ class _ConvBase(nn.Module):
                 w_all = k.permute(1, 0, 2).reshape(self.in_channels, 8 * self.out_channels).contiguous()
                 d['gen_w'] = [w_all] if w_all.shape[1] <= 128 else [w_all[:, :128].contiguous(), w_all[:, 128:].contiguous()]
                 b_all = None if b is None else b.repeat(8)
+                d['gen_w_all'], d['gen_b_all'] = w_all, b_all        # (the bf16 inference path packs its column windows from these)
                 d['gen_b'] = [b_all] if (b_all is None or b_all.numel() <= 128) else [b_all[:128].contiguous(), b_all[128:].contiguous()]
             if not (self.GENERATIVE or self.TRANSPOSED) and self.ks == 3 and _split_k3_ok(self.in_channels, 0, self.out_channels):
                 wt = torch.zeros((self.in_channels, 32), dtype=k.dtype, device=k.device)
@@ -920,6 +989,55 @@ class _ConvBase(nn.Module):
         # flat vector by the top-k pruning, which needs it contiguous
         return out.contiguous() if self.out_channels < 8 else out
 
+    # set by mark_bf16_producers: the next layer reads this one's output as a bf16 operand, so a bf16 evaluation of this layer also
+    # writes the bf16 companion of its output (otherwise the consumer casts)
+    _bf16_out = False
+
+    def _forward_bf16(self, x: SparseTensor, cm: CoordinateManager, src: _Map, dst: _Map, table, kind: str, form: str, d: dict,
+                      ep: dict) -> SparseTensor:
+        """the layer on fpcc_conv_bf16_fused (inside conv_inference_dtype(torch.bfloat16); an eligible shape).  The same launch forms as
+        _forward_fused; the tables are indexed by output row (a row order only says which rows share a block)."""
+        if form not in ('gen', 'plain'):
+            raise RuntimeError(f'a bf16-eligible layer in form {form!r}')            # the eligible set excludes 'split' and 'pad'
+        xb = x.bf16_parts()
+        x1, x2 = xb[0], (xb[1] if len(xb) > 1 else None)
+        c_in, c_out = sum(p.shape[1] for p in xb), self.out_channels
+        w = d['w']
+        want = True if self._bf16_out else None
+        kw = dict(x2=x2, out_bf16=want, **ep)
+        if kind == 'gen' and form == 'gen' and self.GENERATIVE:
+            # the packed dense form: [n, C_in] @ [C_in, 8 * C_out], in column windows of at most 128 (the fp32 path's halves)
+            width = 8 * c_out
+            out = torch.empty((src.n, width), dtype=torch.float32, device=x1.device)
+            comp = torch.empty((src.n, width), dtype=torch.bfloat16, device=x1.device) if want else None
+            w_all, b_all = d['gen_w_all'], d['gen_b_all']
+            for off in range(0, width, 128):
+                cols = min(128, width - off)
+                ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w_all, 1, c_in, cols, src_width=width, src_off=off), cols, src.n,
+                                    bias=None if b_all is None else b_all[off:off + cols], act=ep['act'], slope=ep['slope'],
+                                    clip=ep['clip'], out=out[:, off:off + cols], out_bf16=None if comp is None else comp[:, off:off + cols])
+            res = (out.view(8 * src.n, c_out), None if comp is None else comp.view(8 * src.n, c_out))
+        elif kind == 'gen':
+            res = ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w, 8, c_in, c_out), c_out, src.n, groups=8, **kw)
+        elif kind == 'k2s2T':
+            res = ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w, 8, c_in, c_out), c_out, src.n, groups=8, out_map=table, om_os=8,
+                                      om_gs=1, out_rows=dst.n, **kw)
+        elif kind == 'k1':
+            res = ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w, 1, c_in, c_out), c_out, src.n, **kw)
+        elif kind == 'k3':
+            ro = cm._row_order(src)
+            res = ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w, 27, c_in, c_out), c_out, src.n, nbr=cm._nbr27(src), n_offsets=27,
+                                      nbr_ks=src.n, nbr_os=1, row_order=ro, **kw)
+        else:   # kernel 2, stride 2: the parents in child-pattern order on large maps
+            ro, _ = cm._k2_order(src, want_table=False)
+            res = ops.conv_bf16_fused(x1, ops.packed_weights_bf16(w, 8, c_in, c_out), c_out, dst.n, nbr=table, n_offsets=8, nbr_ks=1,
+                                      nbr_os=8, row_order=ro, **kw)
+        out, comp = res if isinstance(res, tuple) else (res, None)
+        t = SparseTensor(out, coordinate_map_key=dst.key, coordinate_manager=cm)
+        if comp is not None:
+            t._bf16 = [(comp, ops._stream())]
+        return t
+
     def _forward_fused(self, x: SparseTensor, cm: CoordinateManager, src: _Map, coordinates: Optional[CoordinateMapKey], act: _Act,
                        clip: float, plan_rows: int) -> SparseTensor:
         """inference path: one fused launch.  plan_rows: the row count PAD_MIN_ROWS is compared with (the map's, or its clouds')"""
@@ -933,6 +1051,11 @@ class _ConvBase(nn.Module):
         kw = dict(x2=x2, pack=True, **ep)
         kind, dst, table = self._resolve(cm, src, coordinates)
         form, shape = _layer_form(kind, c1, c2, c_out, plan_rows)
+        if inference_dtype() is torch.bfloat16 and ops.bf16_inference_eligible(kind, c1, c2, c_out) and \
+                (self.GENERATIVE or kind != 'gen' or c_out >= 32):
+            # (the last clause: a TRANSPOSED module onto a generated map has no side-by-side weights -- the exception _layer_form
+            # names -- so it is the groups = 8 launch, which needs 32 columns per group; a property of the module, not of a row count)
+            return self._forward_bf16(x, cm, src, dst, table, kind, form, d, ep)
         if kind == 'gen':
             if form == 'gen' and self.GENERATIVE:
                 # all 8 octant kernels side by side: one dense GEMM [n, C_in] @ [C_in, 8*C_out]; its row-major output IS
@@ -993,6 +1116,30 @@ class _ConvBase(nn.Module):
 
 class MinkowskiConvolution(_ConvBase):
     pass
+
+
+def mark_bf16_producers(model: nn.Module) -> int:
+    """For a model that is going to run inside conv_inference_dtype(torch.bfloat16): wherever two convolution blocks follow each other in an
+    nn.Sequential and the second is a bf16-eligible single-source layer, the first is asked to write the bf16 companion of its output
+    (if it runs on the bf16 entry itself), which saves the consumer's cast.  Changes no result -- the companion equals the cast bit for
+    bit -- and nothing outside the context.  -> the number of layers marked"""
+    marked = 0
+    for seq in model.modules():
+        if not isinstance(seq, nn.Sequential):
+            continue
+        blocks = list(seq)
+        for a, b in zip(blocks[:-1], blocks[1:]):
+            ca, cb = getattr(a, 'conv', None), getattr(b, 'conv', None)
+            if not isinstance(ca, _ConvBase) or not isinstance(cb, _ConvBase) or getattr(a, 'bn', None) is not None:
+                continue
+            act = getattr(a, 'act_module', None)
+            if act is not None and not isinstance(act, (MinkowskiPReLU, MinkowskiReLU)):
+                continue                                  # an unfused activation makes a new tensor: the companion would be dropped
+            kind = 'gen' if cb.GENERATIVE else 'k2s2T' if cb.TRANSPOSED else {1: 'k1', 3: 'k3'}.get(cb.ks, 'k2s2')
+            if ca.out_channels == cb.in_channels and ops.bf16_inference_eligible(kind, cb.in_channels, 0, cb.out_channels):
+                ca._bf16_out = True
+                marked += 1
+    return marked
 
 
 def _fusable_in_training(act: _Act) -> bool:

@@ -155,6 +155,9 @@ _SIGS = {
     'fpcc_conv_wgrad_bf16_ws_bytes': (_i64, [_i32, _i32, _i32, _i32, _i64]),
     'fpcc_conv_wgrad_bf16': (_i32, [_vp, _i32, _i32, _vp, _i32, _i32, _vp, _i32, _i64, _i64, _vp, _i64, _i64, _i32, _i64, _vp, _vp,
                                     _i32, _vp, _i64, _vp]),
+    'fpcc_conv_bf16_fused': (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _i64,
+                                    _vp, _i64, _vp, _i64, _i64, _i32, _vp, _f32, _vp, _vp]),
+    'fpcc_conv_bf16_fused_launches': (_i64, []),
 }
 HIP_SYMBOLS = tuple(_SIGS) + ('fpcc_last_error',)
 _BLOCKING_ENTRY_POINTS = ('fpcc_hilbert3d_encode', 'fpcc_conv_debug_stamps', 'fpcc_conv_i8_debug_stamps', 'fpcc_int_init')
@@ -1299,6 +1302,99 @@ def conv_bf16(x: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out: int, *
                              om_os, om_gs, po, ldo, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
                              _dev(row_order, torch.int32, 'row_order', True), None, 0, _stream()))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# opt-in bfloat16 inference (conv_bf16_fused.hip): the codecs' inference_dtype = 'bfloat16'
+
+# Version of the rule below.  The set of layers that run on the bf16 entry is part of the stream format of that mode: a stream written
+# under one profile decodes only under the same one (the codec writes this number behind the marked numerics byte).
+FPCC_BF16_PROFILE_VERSION = 1
+
+_BF16_KINDS = ('k1', 'k3', 'k2s2', 'k2s2T', 'gen')
+# Shapes the entry takes that were taken out before profile version 1 was frozen, by the keep rule (DESIGN.md 8.2,
+# profiles/infer_bf16.md): a shape stays only if its bf16 calls, with the casts they cause, summed over the 1 M-voxel frame AND over the
+# measured rate points (baseline_r1, expanded_r3, baseline_r5), are not slower than its fp32 calls.  (kind, c1, c2, c_out)
+_BF16_REMOVED = frozenset({('gen', 128, 0, 32), ('k2s2', 128, 0, 128), ('k2s2T', 128, 0, 128), ('k1', 64, 0, 32), ('k1', 128, 0, 64)})
+
+
+def bf16_inference_eligible(kind: str, c1: int, c2: int, c_out: int) -> bool:
+    """Whether a _ConvBase layer of this kind ('k1' | 'k3' | 'k2s2' | 'k2s2T' | 'gen') and these channel counts (c1 + c2 in, c_out out,
+    the LAYER's counts) runs on fpcc_conv_bf16_fused inside engine.conv_inference_dtype(torch.bfloat16).  A pure function of the kind
+    and the channel counts and of nothing else -- never of a row count: encoder and decoder may batch different clouds together
+    (engine._pad_plan states the invariant).  The shapes are the ones the entry takes; a generative layer counts with the 8 * c_out
+    columns of its packed dense form when it has one (two column windows of 128 when that is 256) -- less the shapes of _BF16_REMOVED.
+    No shape that engine._layer_form evaluates as 'split' or 'pad' is in the set (those need c_out == 1, or channel counts the matrix
+    pipe does not take).
+    ONE exception lives at the call site (engine._ConvBase._forward_fused), because it is a property of the module class and not of
+    these four arguments: kind 'gen' is also what a TRANSPOSED module onto a generated map resolves to, and such a module has no
+    side-by-side weights -- it is the groups = 8 launch, which needs c_out >= 32.  With c_out in {4, 8, 16} this function says True
+    (the generative module's packed form) and that module stays fp32.  No shipped configuration has such a layer."""
+    if kind not in _BF16_KINDS or c1 < 32 or c1 % 32 or c2 < 0 or c2 % 32 or (kind, c1, c2, c_out) in _BF16_REMOVED:
+        return False
+    if kind == 'gen' and c2 == 0 and 8 * c_out in (32, 64, 128, 256):
+        return True
+    return c_out in (32, 64, 128, 256)
+
+
+def conv_bf16_fused_launches() -> int:
+    """launches of fpcc_conv_bf16_fused by this process so far"""
+    return int(lib().fpcc_conv_bf16_fused_launches())
+
+
+# Packed bf16 images of inference weights, one per (weight tensor, column window): modelled on _PACKED above.  Key: the storage address,
+# the element count and the shape the image is cut to; the entry holds the SOURCE TENSOR itself, so while the entry lives that address
+# cannot be handed to another tensor and the key cannot name stale data; a tensor written in place is caught by `_version`, which is
+# compared on every hit.  Shared by every serving context that runs the same model (the contexts share the weights' storage).
+_PACKED_BF16: 'collections.OrderedDict' = collections.OrderedDict()
+
+
+def packed_weights_bf16(w: torch.Tensor, n_mats: int, c_in: int, c_out: int, src_width: Optional[int] = None, src_off: int = 0) -> torch.Tensor:
+    """cached pack_weights_bf16(w, n_mats, c_in, c_out, src_width=, src_off=) of weights that stay put between calls"""
+    key = (w.data_ptr(), w.numel(), n_mats, c_in, c_out, src_width, src_off)
+    ent = _PACKED_BF16.get(key)
+    if ent is not None and ent[1] == w._version:
+        _PACKED_BF16.move_to_end(key)
+        return ent[2]
+    out = pack_weights_bf16(w, n_mats, c_in, c_out, src_width=src_width, src_off=src_off)
+    _PACKED_BF16[key] = (w, w._version, out)
+    while len(_PACKED_BF16) > _PACKED_MAX:
+        _PACKED_BF16.popitem(last=False)
+    return out
+
+
+def conv_bf16_fused(x1: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out: int, *, x2: Optional[torch.Tensor] = None,
+                    nbr: Optional[torch.Tensor] = None, n_offsets: int = 1, nbr_ks: int = 0, nbr_os: int = 1,
+                    bias: Optional[torch.Tensor] = None, groups: int = 1, out_map: Optional[torch.Tensor] = None,
+                    om_os: int = 0, om_gs: int = 1, out: Optional[torch.Tensor] = None, out_rows: Optional[int] = None,
+                    act: int = ACT_NONE, slope: Optional[torch.Tensor] = None, clip: float = 0.0,
+                    row_order: Optional[torch.Tensor] = None, out_bf16=None):
+    """conv_f32's layer on bfloat16 rows x1 (and x2: one operand [x1 | x2]) and a packed bf16 image of w [groups, n_offsets, c1 + c2, c_out]
+    (pack_weights_bf16 / packed_weights_bf16); fp32 out, which may be a column window of a wider matrix; see fpcc_conv_bf16_fused.
+    out_bf16: None, True (allocate) or a bfloat16 [rows, c_out] tensor / window that receives out.bfloat16().  -> out, or
+    (out, companion) when out_bf16 is given"""
+    p1, c1, ld1 = _rows2d_bf16(x1, 'x1')
+    if x2 is not None:
+        p2, c2, ld2 = _rows2d_bf16(x2, 'x2')
+    else:
+        p2, c2, ld2 = None, 0, 0
+    if w_packed.dtype != torch.bfloat16 or not w_packed.is_cuda or not w_packed.is_contiguous() or \
+            w_packed.numel() != groups * n_offsets * (c1 + c2) * c_out:
+        raise ValueError(f'packed weights must hold {groups} x {n_offsets} x {c1 + c2} x {c_out} bfloat16')
+    out, po, ldo, om_os = _conv_out(out, out_rows, n_out, groups, c_out, om_os, x1.device)
+    comp, pb, ldb = None, None, 0
+    if out_bf16 is not None and out_bf16 is not False:
+        comp = torch.empty((out.shape[0], c_out), dtype=torch.bfloat16, device=x1.device) if out_bf16 is True else out_bf16
+        pb, cb, ldb = _rows2d_bf16(comp, 'out_bf16')
+        if cb != c_out or comp.shape[0] != out.shape[0]:
+            raise ValueError('bf16 companion shape mismatch')
+    fn = lib().fpcc_conv_bf16_fused
+    call = (p1, c1, ld1, p2, c2, ld2, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os, w_packed.data_ptr(),
+            _dev(bias, torch.float32, 'bias', True), c_out, groups, _dev(out_map, torch.int32, 'out_map', True), om_os, om_gs,
+            po, ldo, pb, ldb, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
+            _dev(row_order, torch.int32, 'row_order', True), _stream())
+    _untraced_launch(fn, call)              # (not listed in a conv trace: tools/infer_bf16_ab.py times these layers at the engine's call)
+    return out if comp is None else (out, comp)
 
 
 def conv_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, n: int, *, nbr: Optional[torch.Tensor] = None, n_offsets: int = 1,

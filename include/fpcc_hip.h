@@ -991,6 +991,34 @@ int fpcc_conv_wgrad_bf16(const uint16_t *x, int c_in, int ldx, const uint16_t *d
                          const int32_t *out_map, int64_t om_os, int64_t om_gs, int groups, int64_t n,
                          const int32_t *row_order, float *dw, int accumulate, void *ws, int64_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------ */
+/* bfloat16 INFERENCE, opt-in (conv_bf16_fused.hip).  The default inference path stays fp32 and never calls this.  */
+/* ------------------------------------------------------------------------------------------------------------ */
+/* One convolution layer as fpcc_conv_bf16 evaluates it, in the forms the engine's fused inference launches take:
+ *   two sources   x1 [*, c1] and, when c2 != 0, x2 [*, c2] (bf16 rows, strides ld1 / ld2 in bf16, multiples of 8) are ONE operand
+ *                 [x1 | x2]; w_packed is the image fpcc_conv_pack_weights_bf16 makes of the groups * n_offsets matrices
+ *                 [c1 + c2][c_out], so x1's 16-channel steps come before x2's;
+ *   epilogue      bias, PReLU / ReLU and clamp as fpcc_conv_f32; nbr / out_map / groups / row_order as fpcc_conv_bf16 (with a row
+ *                 order the tables are still indexed by output row);
+ *   out           fp32, row pitch ldo >= c_out floats: a call may write a column window of a wider matrix;
+ *   out_bf16      NULL, or bf16 rows of pitch ldb >= c_out that receive the same finished values rounded to nearest even -- bit for
+ *                 bit what fpcc_cast_f32_bf16 makes of `out`.  A cache of that cast for a following bf16 layer, never a definition.
+ * Summation chain of every output element: offsets ascending; with 8 or more offsets the four contiguous offset groups
+ * [ceil(g K / 4), ceil((g + 1) K / 4)), each a chain from zero, added as ((g0 + g1) + g2) + g3; 16-wide K steps ascending inside an
+ * offset.  For c2 == 0 the fp32 output is therefore bit for bit fpcc_conv_bf16's on the same operands, for two sources fpcc_conv_bf16's
+ * on the concatenated rows.  No atomics; same bits twice, under any row order and whatever other rows share the launch.  These bits
+ * are part of the stream format of a codec run with inference_dtype = 'bfloat16' (FPCC_BF16_PROFILE_VERSION of hipops.py names the set
+ * of layers that take this entry there), and of no other stream.
+ * c1 a multiple of 32, c2 0 or a multiple of 32, c_out in {32, 64, 128, 256}, 1 <= n_offsets <= 32, 1 <= groups <= 8.
+ * fpcc_conv_bf16_fused_launches: diagnostics, launches of this entry by this process so far (tests of the routing). */
+int fpcc_conv_bf16_fused(const uint16_t *x1, int c1, int64_t ld1, const uint16_t *x2, int c2, int64_t ld2,
+                         const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                         const uint16_t *w_packed, const float *bias, int c_out, int groups,
+                         const int32_t *out_map, int64_t om_os, int64_t om_gs,
+                         float *out, int64_t ldo, uint16_t *out_bf16, int64_t ldb, int64_t n_out,
+                         int act, const float *slope, float clip, const int32_t *row_order, void *stream);
+long long fpcc_conv_bf16_fused_launches(void);
+
 #ifdef __cplusplus
 }
 #endif
