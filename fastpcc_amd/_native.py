@@ -42,6 +42,8 @@ def host():
             'fpcc_rans_binary_encode_multi': [vp, vp, vp, i64, vp, i64, vp, i32],
             'fpcc_rans_binary_il_encode': [vp, vp, i64, i32, i32, vp, i64],
             'fpcc_rans_binary_il_decode': [vp, i64, vp, i64, vp],
+            'fpcc_rans_rows_il_encode': [vp, vp, i64, i32, i32, i32, vp, i64],
+            'fpcc_rans_rows_il_decode': [vp, i64, vp, i64, i32, vp],
             'fpcc_simple_enc_push': [vp, vp, i64, i64, vp, i64],
             'fpcc_simple_enc_push_bin': [vp, vp, i64, vp, i64],
             'fpcc_simple_enc_push_ranges': [vp, vp, vp, i64],
@@ -89,7 +91,7 @@ HOST_SYMBOLS = (
     'fpcc_simple_enc_finish', 'fpcc_simple_dec_new', 'fpcc_simple_dec_free', 'fpcc_simple_dec_pop',
     'fpcc_simple_dec_pop_bin', 'fpcc_simple_dec_tell', 'fpcc_pool_new', 'fpcc_pool_free', 'fpcc_pool_binary_encode',
     'fpcc_pool_histogram_encode', 'fpcc_pool_table_decode', 'fpcc_pool_binary_decode', 'fpcc_progress_wait', 'fpcc_pool_wait',
-    'fpcc_rans_binary_il_encode', 'fpcc_rans_binary_il_decode')
+    'fpcc_rans_binary_il_encode', 'fpcc_rans_binary_il_decode', 'fpcc_rans_rows_il_encode', 'fpcc_rans_rows_il_decode')
 
 
 def hip():

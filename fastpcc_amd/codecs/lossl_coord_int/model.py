@@ -10,6 +10,8 @@ What differs is where bytes move:
   * decode: CDF rows are produced by one fused kernel per level and copied once; the serial rANS chain runs on the host
     as in the reference (it needs the whole row of every symbol);
   * every conv/linear carries its fixed-point epilogue (one launch per layer).
+`Config.occupancy_stream_format = 'interleaved'` (opt-in; INTEGRATION.md, "Interleaved row blocks") replaces the one rANS state by
+interleaved row blocks coded and decoded on the device: neither ranges nor rows cross PCIe, a level's read-back is its children counts.
 """
 import io
 import math
@@ -28,7 +30,7 @@ from ...int_sparse_conv import LinearIn8W8Out8, LinearIn8W8Out32, LinearPReLUIn8
     PReLUIn32Out32, RequantFxpToScaledInt8, ROW_ORDER_MIN_ROWS, ROW_ORDER_WINDOW_LOG2, SharedFxpShift, SparseConvIn8W8Out8, \
     SparseConvIn8W8Out32, SparseConvPReLUIn8W8Out8, SparseConvPReLUIn8W8Out32, SparseResBlockIn32W8Out32, SparseTensor, \
     _kernel_table, sparse_conv_in8w8out32
-from ...rans_coder import RansDecoder, RansEncoder
+from ...rans_coder import InterleavedRowCoder, RansDecoder, RansEncoder
 from .model_config import Config
 
 _DENSE = (PReLUIn32Out32, RequantFxpToScaledInt8, LinearIn8W8Out8, LinearIn8W8Out32, LinearPReLUIn8W8Out8,
@@ -577,6 +579,14 @@ class Model(nn.Module):
         # slower than the chunked host path on this codec (profiles/r02/device_rans.md), hence off by default
         self.device_decoder = False
         self._clouds = None            # decompress_many: {'decoders', 'rows' (per cloud, of the level being decoded), 'threads'}
+        # 'interleaved': every coded level is one interleaved row block per cloud, coded and decoded on the device (INTEGRATION.md,
+        # "Interleaved row blocks"); what a DEcoder does is read from the stream, whatever this says
+        self.occupancy_format = getattr(cfg, 'occupancy_stream_format', 'reference')
+        if self.occupancy_format not in ('reference', 'interleaved'):
+            raise ValueError("occupancy_stream_format must be 'reference' or 'interleaved'")
+        if self.occupancy_format == 'interleaved' and type(self) is not Model:
+            raise NotImplementedError(f'{type(self).__module__}: interleaved row blocks are built for lossl_coord_int only')
+        self._il = None                # decoding an interleaved stream: {'dev', 'blocks'[level][cloud] = (bytes, at), 'level', 'rows'}
         self._extra_encoders: List[RansEncoder] = []
 
     # ---------------------------------------------------------------------------------------------------------------
@@ -650,6 +660,8 @@ class Model(nn.Module):
         ~55 GB/s) hides behind the decode instead of preceding it."""
         rows_d = ops.logits_to_cdf16(logits.contiguous(), PRE_SHIFT)
         n = rows_d.shape[0]
+        if self._il is not None:
+            return self._il_decode_level(rows_d)
         if self.device_decoder:
             # the CDF rows stay where they were made: one wave decodes the level's symbols on the device, 4 bytes come back
             sym, children = ops.simple_dec_pop_dev(self._dev_state, self._dev_stream, self._dev_stream_len, rows_d)
@@ -697,6 +709,83 @@ class Model(nn.Module):
         out = out_h.to(logits.device, non_blocking=True)
         out._fpcc_children = _children_count(out_h.numpy()) if clouds is None else sum(clouds['rows'])
         return out
+
+    # -- interleaved row blocks ("Interleaved row blocks") ----------------------------------------------------------
+    IL_FORMAT = 1
+
+    def _il_decode_level(self, rows_d: torch.Tensor) -> torch.Tensor:
+        """one level of an interleaved stream: the rows stay where fpcc_logits_to_cdf16 wrote them, every cloud's block of the level is
+        decoded by one launch (a cloud is a segment), and ONE read-back -- the clouds' children counts and the status word -- sizes the
+        next level"""
+        il = self._il
+        n, c = rows_d.shape
+        counts = il['rows']
+        if il['level'] >= len(il['blocks']) or n != sum(counts):
+            raise ValueError('interleaved stream: the level does not hold the rows its blocks account for')
+        tables, sym0 = [], 0
+        for cloud, (block, at) in enumerate(il['blocks'][il['level']]):
+            tables.append(InterleavedRowCoder.chunk_table(block, counts[cloud], c, at, sym0, cloud))      # ValueError: malformed header
+            sym0 += counts[cloud]
+        il['level'] += 1
+        table = torch.from_numpy(np.concatenate(tables)).to(rows_d.device, non_blocking=True)
+        sym, got = ops.rans_rows_il_decode_dev(il['dev'], table, rows_d, len(counts))
+        got = got.tolist()                                    # the level's one read-back
+        if got[-1] != 0:
+            raise ValueError(f'corrupt interleaved occupancy block (device decoder status {got[-1]})')
+        il['rows'] = [int(v) for v in got[:-1]]
+        sym._fpcc_children = sum(il['rows'])
+        return sym
+
+    def _il_parse(self, data: bytes, levels: int):
+        """an interleaved stream -> (n_bottom, bottom section, [block per level]); ValueError before any payload byte is read"""
+        if len(data) < 16 or data[8] != self.IL_FORMAT:
+            raise ValueError('interleaved stream: unknown format byte or a stream shorter than its header')
+        n_bottom, n_blocks = int.from_bytes(data[9:11], 'little'), data[11]
+        if n_bottom < 1 or n_blocks != levels:
+            raise ValueError('interleaved stream: no bottom voxel, or another number of blocks than this configuration codes levels')
+        at, parts = 12, []
+        for _ in range(1 + n_blocks):
+            if at + 4 > len(data):
+                raise ValueError('interleaved stream: a section reaches past the stream')
+            length = int.from_bytes(data[at:at + 4], 'little')
+            if length > len(data) - at - 4:
+                raise ValueError('interleaved stream: a section reaches past the stream')
+            parts.append((at + 4, length))
+            at += 4 + length
+        if at != len(data):
+            raise ValueError('interleaved stream: bytes left over')
+        bottom = data[parts[0][0]: parts[0][0] + parts[0][1]]
+        if len(bottom) < 4:
+            raise ValueError('interleaved stream: no bottom section')
+        return n_bottom, bottom, parts[1:]
+
+    def _il_encode(self, pending, seg_edges: List[int]):
+        """the pending (start, freq - 1) of all levels, on the device -> one encode call; nothing is synchronised.  -> what `_il_blocks`
+        reads after the caller's synchronise"""
+        start = torch.cat([s for s, _ in pending])
+        freq = torch.cat([f for _, f in pending])
+        out, meta, offsets = ops.rans_rows_il_encode_dev(start, freq, 255, seg_edges)
+        out_h = torch.empty(out.numel(), dtype=torch.uint8, pin_memory=True)
+        meta_h = torch.empty(meta.numel(), dtype=torch.int64, pin_memory=True)
+        out_h.copy_(out, non_blocking=True)
+        meta_h.copy_(meta, non_blocking=True)
+        return out_h, meta_h, offsets
+
+    @staticmethod
+    def _il_blocks(coded) -> List[bytes]:
+        out_h, meta_h, offsets = coded
+        meta = meta_h.tolist()
+        if meta[-1] != 0:
+            raise ValueError('a range that leaves [0, 65536] cannot be coded')
+        raw = out_h.numpy()
+        return [raw[at: at + n].tobytes() for at, n in zip(offsets[:-1], meta[:-1])]
+
+    def _il_stream(self, offset3, n_bottom: int, bottom_section: bytes, blocks: List[bytes]) -> bytes:
+        if len(blocks) > 255 or not 1 <= n_bottom <= 0xffff:
+            raise ValueError('interleaved stream: at most 255 levels and 65535 bottom voxels')
+        head = b''.join(int(v).to_bytes(2, 'little') for v in offset3) + (0).to_bytes(2, 'little') + bytes([self.IL_FORMAT]) + \
+            n_bottom.to_bytes(2, 'little') + bytes([len(blocks)])
+        return head + b''.join(len(p).to_bytes(4, 'little') + p for p in [bottom_section, *blocks])
 
     def rans_encode_fea(self, quantized_cdf: np.ndarray, rounded: np.ndarray, encoder: Optional[RansEncoder] = None):
         enc = encoder or self.rans_encoder
@@ -760,8 +849,19 @@ class Model(nn.Module):
                 cur_rec, logits, symbols = block.compress(cur_rec, strided[idx: idx + block.pred_steps], self.bin2oct_kernel)
             pending.append(ops.logits_to_ranges(logits.contiguous(), PRE_SHIFT, symbols.contiguous()))
 
-        # one synchronising transfer: 4 bytes per symbol + the coarsest coordinates
         sizes = [s.shape[0] for s, _ in pending]
+        if self.occupancy_format == 'interleaved':
+            # the ranges stay on the device: one encode call over all levels (a level is a segment), one synchronising copy of the
+            # blocks' lengths and bytes + the coarsest coordinates
+            coded = self._il_encode(pending, [0, *np.cumsum(sizes).tolist()])
+            bottom_h = torch.empty(bottom_vals.shape, dtype=torch.int32, pin_memory=True)
+            bottom_h.copy_(bottom_vals, non_blocking=True)
+            offset_h = coord_offset.cpu()
+            torch.cuda.current_stream().synchronize()
+            bottom_np = bottom_h.numpy()
+            self.rans_encode_fea(self.bottom_cdf(bottom_np), bottom_np.astype(np.uint16))
+            return self._il_stream(offset_h.tolist(), bottom_np.shape[0] // 3, self.rans_encoder.flush(), self._il_blocks(coded))
+        # one synchronising transfer: 4 bytes per symbol + the coarsest coordinates
         start_h = torch.empty(sum(sizes), dtype=torch.int16, pin_memory=True)
         freq_h = torch.empty(sum(sizes), dtype=torch.int16, pin_memory=True)
         start_h.copy_(torch.cat([s for s, _ in pending]), non_blocking=True)
@@ -850,6 +950,8 @@ class Model(nn.Module):
                 cur_rec, logits, symbols = block.compress(cur_rec, strided[idx: idx + block.pred_steps], self.bin2oct_kernel)
             pending.append(ops.logits_to_ranges(logits.contiguous(), PRE_SHIFT, symbols.contiguous()))
         sizes = [s.shape[0] for s, _ in pending]
+        if self.occupancy_format == 'interleaved':
+            return self._il_compress_many(pending, sizes, level_rows, levels, top, offsets, B)
         start_h = torch.empty(sum(sizes), dtype=torch.int16, pin_memory=True)
         freq_h = torch.empty(sum(sizes), dtype=torch.int16, pin_memory=True)
         start_h.copy_(torch.cat([s for s, _ in pending]), non_blocking=True)
@@ -884,6 +986,52 @@ class Model(nn.Module):
             return head + enc.flush()
         return list(self._thread_pool(B).map(code_cloud, range(B)))
 
+    def _il_compress_many(self, pending, sizes, level_rows, levels: int, top, offsets, B: int) -> List[bytes]:
+        """the interleaved half of compress_many: every (level, cloud) pair is a segment of ONE encode call (chunks never span clouds,
+        the policy depends on the segment's size alone: each cloud's blocks are what `compress` writes for it alone)"""
+        rows = np.array([level_rows[idx] for idx in range(levels, 0, -1)], dtype=np.int64)     # [coded levels (coarse -> fine), B]
+        if (rows.sum(1) != np.array(sizes)).any():
+            raise RuntimeError('cloud row counts do not add up to the levels')
+        coded = self._il_encode(pending, [0, *np.cumsum(rows.reshape(-1)).tolist()])
+        bottom_h = torch.empty((top.C.shape[0], 3), dtype=torch.int32, pin_memory=True)
+        bottom_h.copy_(top.C[:, 1:], non_blocking=True)
+        offset_h = torch.empty((B, 3), dtype=offsets.dtype, pin_memory=True)
+        offset_h.copy_(offsets[:, 1:], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        blocks = self._il_blocks(coded)                                     # segment l * B + c
+        bottom_np, offs = bottom_h.numpy(), offset_h.numpy()
+        bottom_at = np.concatenate(([0], np.cumsum(rows[0])))               # the coarsest coded level's rows ARE the bottom voxels
+        out = []
+        for c in range(B):
+            mine = bottom_np[bottom_at[c]: bottom_at[c + 1]].reshape(-1)
+            self.rans_encode_fea(self.bottom_cdf(mine), mine.astype(np.uint16))
+            out.append(self._il_stream(offs[c].tolist(), int(rows[0, c]), self.rans_encoder.flush(), blocks[c::B]))
+        return out
+
+    def _il_decompress_many(self, streams: List[bytes], levels: int, device):
+        """the interleaved half of decompress_many: the blocks of all clouds go up in one copy; -> (bottoms, offsets) with self._il set"""
+        bottoms, offsets, parsed = [], [], []
+        for b, data in enumerate(streams):
+            offsets.append([int.from_bytes(data[i:i + 2], 'little') for i in (0, 2, 4)])
+            n_bottom, bottom, parts = self._il_parse(data, levels)
+            self.rans_decoder.flush(bottom)
+            xyz = torch.from_numpy(self.rans_decode_fea(n_bottom * 3).astype(np.int32)).reshape(-1, 3)
+            bottoms.append(F.pad(xyz, (1, 0, 0, 0), value=b))
+            parsed.append(parts)
+        base, at = [], 0
+        for data in streams:
+            base.append(at)
+            at += len(data)
+        self._il = {'dev': ops.stream_to_device(b''.join(streams), device), 'level': 0, 'rows': [b.shape[0] for b in bottoms],
+                    'blocks': [[(streams[c][parsed[c][l][0]: parsed[c][l][0] + parsed[c][l][1]], base[c] + parsed[c][l][0])
+                                for c in range(len(streams))] for l in range(levels)]}
+        return bottoms, offsets
+
+    @staticmethod
+    def _is_interleaved(data: bytes) -> bool:
+        """a cloud has at least one bottom voxel: the reference writes n_bottom >= 1 where the interleaved layout writes 0"""
+        return len(data) >= 8 and data[6] == 0 and data[7] == 0
+
     @ops.no_gc_pause
     @torch.no_grad()
     def decompress_many(self, streams: List[bytes]) -> List[torch.Tensor]:
@@ -894,14 +1042,22 @@ class Model(nn.Module):
             return [self.decompress(streams[0])]
         if B == 0:
             raise RuntimeError('decompress_many() takes a non-empty list of streams')
-        if self.device_decoder:
+        formats = {self._is_interleaved(data) for data in streams}
+        if len(formats) == 2:                                               # both formats in one list: one cloud at a time
+            return [self.decompress(data) for data in streams]
+        interleaved = formats == {True}
+        if interleaved and type(self) is not Model:
+            raise NotImplementedError(f'{type(self).__module__}: interleaved row blocks are built for lossl_coord_int only')
+        if self.device_decoder and not interleaved:
             raise NotImplementedError('the device-side decoder takes one cloud')
         device = self.fold2bin_kernel.device
         skip = self.cfg.skip_top_scales_num
         blocks = self.blocks_dec[skip:]
         levels = self.max_downsample_times - skip
         decoders, bottoms, offsets = [], [], []
-        for b, data in enumerate(streams):
+        if interleaved:
+            bottoms, offsets = self._il_decompress_many(streams, levels, device)
+        for b, data in enumerate([] if interleaved else streams):
             offsets.append([int.from_bytes(data[i:i + 2], 'little') for i in (0, 2, 4)])
             n_bottom = int.from_bytes(data[6:8], 'little')
             dec = RansDecoder()
@@ -909,7 +1065,8 @@ class Model(nn.Module):
             xyz = torch.from_numpy(self.rans_decode_fea(n_bottom * 3, dec).astype(np.int32)).reshape(-1, 3)
             bottoms.append(F.pad(xyz, (1, 0, 0, 0), value=b))
             decoders.append(dec)
-        self._clouds = {'decoders': decoders, 'rows': [b.shape[0] for b in bottoms], 'threads': self._thread_pool(B)}
+        if not interleaved:
+            self._clouds = {'decoders': decoders, 'rows': [b.shape[0] for b in bottoms], 'threads': self._thread_pool(B)}
         try:
             cur_rec = self.get_init_pc(torch.cat(bottoms).to(device), 2 ** levels)
             cur_bins, top_rec, top_stride, cur_bin = [], None, None, None
@@ -932,9 +1089,9 @@ class Model(nn.Module):
                     raise RuntimeError('unexpected final stride')
                 parents = top_rec
             recon = _children_of(parents, self.unfold_kernel, cur_bin)[:, 1:]
-            counts = self._clouds['rows']                                   # after the last level: the clouds' point counts
+            counts = (self._il if interleaved else self._clouds)['rows']    # after the last level: the clouds' point counts
         finally:
-            self._clouds = None
+            self._clouds = self._il = None
         if sum(counts) != recon.shape[0]:
             raise RuntimeError('decoded point counts do not add up')
         offset_t = torch.tensor(offsets, device=device, dtype=torch.int32)
@@ -955,6 +1112,10 @@ class Model(nn.Module):
     @torch.no_grad()
     def decompress(self, compressed_bytes: bytes) -> torch.Tensor:
         device = self.fold2bin_kernel.device
+        if self._is_interleaved(compressed_bytes):                          # the format is the stream's, whatever the option says
+            if type(self) is not Model:
+                raise NotImplementedError(f'{type(self).__module__}: interleaved row blocks are built for lossl_coord_int only')
+            return self._il_decompress(compressed_bytes)
         coord_offset = [int.from_bytes(compressed_bytes[i:i + 2], 'little') for i in (0, 2, 4)]
         n_bottom = int.from_bytes(compressed_bytes[6:8], 'little')
         payload = compressed_bytes[8:]
@@ -992,6 +1153,33 @@ class Model(nn.Module):
             parents = top_rec
         recon = _children_of(parents, self.unfold_kernel, cur_bin)[:, 1:]
         return recon + torch.tensor(coord_offset, device=device, dtype=torch.int32)[None]
+
+    def _il_decompress(self, data: bytes) -> torch.Tensor:
+        """one cloud of an interleaved stream: the traversal of decompress_many with one segment"""
+        device = self.fold2bin_kernel.device
+        skip = self.cfg.skip_top_scales_num
+        blocks = self.blocks_dec[skip:]
+        levels = self.max_downsample_times - skip
+        bottoms, offsets = self._il_decompress_many([data], levels, device)
+        try:
+            cur_rec = self.get_init_pc(bottoms[0].to(device), 2 ** levels)
+            cur_bins, top_rec, top_stride, cur_bin = [], None, None, None
+            for idx in range(levels, 0, -1):
+                block = self._block(idx, blocks)
+                if isinstance(block, OneScalePredictor):
+                    cur_rec, cur_bin = block.decompress(cur_rec, self.bin2oct_kernel, self.unfold_kernel, self.rans_decode_oct,
+                                                        if_upsample=idx != 1 and block.if_upsample,
+                                                        next_block=self._block(idx - 1, blocks) if idx > 1 else None)
+                else:
+                    cur_bins.append(cur_bin)
+                    cur_rec, cur_bin, top_rec, top_stride = block.decompress(
+                        cur_rec, cur_bins, top_rec, top_stride, self.bin2oct_kernel, self.unfold_kernel, self.rans_decode_oct)
+            if (cur_rec.stride[0] if top_rec is None else top_stride) != 2:
+                raise RuntimeError('unexpected final stride')
+            recon = _children_of(cur_rec.C if top_rec is None else top_rec, self.unfold_kernel, cur_bin)[:, 1:]
+        finally:
+            self._il = None
+        return recon + torch.tensor(offsets[0], device=device, dtype=torch.int32)[None]
 
     def decompress_partitions(self, concat_bytes: bytes) -> torch.Tensor:
         streams, pos = [], 0

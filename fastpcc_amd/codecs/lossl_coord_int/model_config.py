@@ -14,3 +14,11 @@ class Config:
     use_more_ch_for_multi_step_pred: bool = False
     skip_top_scales_num: int = 0
     cal_avs_pc_evalue: bool = False
+    # 'reference': the reference's stream (one LIFO rANS state).  'interleaved': every coded octree level is one interleaved row block,
+    # coded and decoded on the device ("Interleaved row blocks"); read by any decoder of this build, not by the
+    # reference.  Not a key of the reference's YAML.
+    occupancy_stream_format: str = 'reference'
+
+    def __post_init__(self):
+        if self.occupancy_stream_format not in ('reference', 'interleaved'):
+            raise ValueError("occupancy_stream_format must be 'reference' or 'interleaved'")

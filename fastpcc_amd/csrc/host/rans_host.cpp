@@ -1105,4 +1105,123 @@ int64_t fpcc_pool_wait(fpcc_pool *p) {
     return rc;
 }
 
+// ---- interleaved row blocks ("Interleaved row blocks") ----------------------------------------------------------
+// The binary block format's chunks, lanes, rounds and payload order with the SIMPLE coder's per-lane step (ranges out of 2^16 under
+// one CDF row per symbol: fpcc_simple_enc_push_ranges / fpcc_simple_dec_pop above).  A plain statement of the format -- the kernels of
+// csrc/hip/rans_rows_il.hip are checked against it -- not a hot path.
+int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1, int64_t n, int c, int a, int b, uint8_t *out,
+                                 int64_t cap) {
+    if (!out || n < 0 || cap < 0 || c < 2 || c > 256 || (n > 0 && (!start || !freq_m1))) return FPCC_HOST_E_ARG;
+    il_policy(n, a, b);
+    IlHeader h;
+    if (!il_geometry(a, b, n, h)) return FPCC_HOST_E_ARG;
+    const int lanes = h.lanes();
+    int64_t at = 8 + 4 * h.chunks;
+    if (cap < at) return FPCC_HOST_E_BUFFER;
+    out[0] = static_cast<uint8_t>(0xB0 | a);
+    out[1] = static_cast<uint8_t>(b);
+    store_le32(out + 2, static_cast<uint32_t>(n));
+    out[6] = static_cast<uint8_t>(c);
+    out[7] = static_cast<uint8_t>(c >> 8);
+    std::vector<uint8_t> slot(static_cast<size_t>(4 * lanes + 2 * h.per_chunk));
+    for (int64_t k = 0; k < h.chunks; ++k) {
+        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
+        const int64_t slot_bytes = 4 * lanes + 2 * m;
+        uint32_t x[kIlMaxLanes];
+        for (int l = 0; l < lanes; ++l) x[l] = kLow;
+        int64_t wp = slot_bytes;
+        for (int64_t r = (m + lanes - 1) / lanes - 1; r >= 0; --r) {
+            const int active = static_cast<int>(std::min<int64_t>(lanes, m - r * lanes));
+            uint8_t first[kIlMaxLanes], second[kIlMaxLanes];       // what the decoder takes in refill step 0 / step 1
+            int k_of[kIlMaxLanes], c1 = 0, c2 = 0;
+            for (int l = 0; l < active; ++l) {
+                const int64_t j = s0 + r * lanes + l;
+                const uint32_t lo = start[j], f = uint32_t(freq_m1[j]) + 1u;
+                if (lo + f > kProbOne) return FPCC_HOST_E_ARG;     // the range leaves the interval (f >= 1 by its representation)
+                const uint32_t ceiling = ((kLow >> kProbBits) << 8) * f;
+                uint32_t v = x[l];
+                uint8_t e[2] = {0, 0};
+                int emitted = 0;
+                while (v >= ceiling) { e[emitted++] = static_cast<uint8_t>(v); v >>= 8; }      // at most twice: v < 2^31, ceiling >= 2^15
+                x[l] = ((v / f) << kProbBits) + v % f + lo;
+                k_of[l] = emitted;
+                first[l] = emitted ? e[emitted - 1] : 0;           // the decoder reads a lane's bytes of a round last-emitted first
+                second[l] = e[0];
+                c1 += emitted >= 1;
+                c2 += emitted >= 2;
+            }
+            wp -= c1 + c2;
+            int64_t at1 = wp, at2 = wp + c1;
+            for (int l = 0; l < active; ++l) {
+                if (k_of[l] >= 1) slot[at1++] = first[l];
+                if (k_of[l] >= 2) slot[at2++] = second[l];
+            }
+        }
+        wp -= 4 * lanes;
+        for (int l = 0; l < lanes; ++l) store_le32(slot.data() + wp + 4 * l, x[l]);
+        const int64_t len = slot_bytes - wp;
+        if (cap - at < len) return FPCC_HOST_E_BUFFER;
+        std::memcpy(out + at, slot.data() + wp, static_cast<size_t>(len));
+        store_le32(out + 8 + 4 * k, static_cast<uint32_t>(len));
+        at += len;
+    }
+    return at;
+}
+
+int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *rows, int64_t n, int c, uint16_t *symbols_out) {
+    if (!block || n < 0 || block_len < 8 || c < 2 || c > 256 || (n > 0 && (!rows || !symbols_out))) return FPCC_HOST_E_ARG;
+    // the header, before a single payload byte is read: tag, a, b, the symbol count and row width the caller expects, K, every length
+    // >= 4 lanes, the lengths summing to what is left of the block
+    if ((block[0] & 0xF8) != 0xB0) return FPCC_HOST_E_ARG;
+    IlHeader h;
+    if (!il_geometry(block[0] & 7, block[1], n, h) || load_le32(block + 2) != static_cast<uint32_t>(n)) return FPCC_HOST_E_ARG;
+    if ((int(block[6]) | int(block[7]) << 8) != c) return FPCC_HOST_E_ARG;
+    const int lanes = h.lanes();
+    if (h.chunks > (block_len - 8) / 4) return FPCC_HOST_E_ARG;
+    int64_t rest = block_len - 8 - 4 * h.chunks;
+    for (int64_t k = 0; k < h.chunks; ++k) {
+        const int64_t len = load_le32(block + 8 + 4 * k);
+        if (len < 4 * lanes || len > rest) return FPCC_HOST_E_ARG;
+        rest -= len;
+    }
+    if (rest != 0) return FPCC_HOST_E_ARG;
+    const uint8_t *payload = block + 8 + 4 * h.chunks;
+    for (int64_t k = 0; k < h.chunks; ++k) {
+        const int64_t len = load_le32(block + 8 + 4 * k);
+        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
+        uint32_t x[kIlMaxLanes];
+        for (int l = 0; l < lanes; ++l) {
+            x[l] = load_le32(payload + 4 * l);
+            if (x[l] < kLow) return FPCC_HOST_E_ARG;                  // not a state any encoder flushes
+        }
+        int64_t pos = 4 * lanes;
+        const int64_t rounds = (m + lanes - 1) / lanes;
+        for (int64_t r = 0; r < rounds; ++r) {
+            const int active = static_cast<int>(std::min<int64_t>(lanes, m - r * lanes));
+            for (int l = 0; l < active; ++l) {
+                const int64_t j = s0 + r * lanes + l;
+                const uint16_t *row = rows + j * c;
+                const uint32_t slot = x[l] & (kProbOne - 1u);
+                int64_t s = 0;
+                for (int e = 0; e < c; ++e) s += row[e] <= slot;
+                s = std::min<int64_t>(s, c - 1);
+                uint32_t lo, hi;
+                edge_range(row, c, static_cast<uint32_t>(s), lo, hi);
+                if (hi <= lo) return FPCC_HOST_E_ARG;                 // the row does not increase at the decoded symbol
+                x[l] = (hi - lo) * (x[l] >> kProbBits) + slot - lo;
+                symbols_out[j] = static_cast<uint16_t>(s);
+            }
+            for (int t = 0; t < kMaxRefill; ++t)
+                for (int l = 0; l < active; ++l)
+                    if (x[l] < kLow) {
+                        const uint32_t byte = pos < len ? payload[pos] : 0u;      // past the chunk's payload: zeros, never another chunk's bytes
+                        ++pos;
+                        x[l] = (x[l] << 8) | byte;
+                    }
+        }
+        payload += len;
+    }
+    return FPCC_HOST_OK;
+}
+
 }  // extern "C"

@@ -132,6 +132,8 @@ _SIGS = {
     'fpcc_simple_dec_pop_dev': (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
     'fpcc_rans_binary_il_encode_dev': (_i64, [_vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     'fpcc_rans_binary_il_decode_dev': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp]),
+    'fpcc_rans_rows_il_encode_dev': (_i64, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'fpcc_rans_rows_il_decode_dev': (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp]),
     'fpcc_device_count': (_i32, []),
     'fpcc_clock_probe': (_i32, [_vp, _i32, _vp]),
     'fpcc_mlp_chain_f32': (_i32, [_vp, _vp]),
@@ -2199,3 +2201,69 @@ def rans_binary_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, prob16
                                              _dev(prob16, torch.int16, 'prob16', n_chunks == 0), n, bits.data_ptr(), counts.data_ptr(), int(n_seg),
                                              counts.data_ptr() + 4 * int(n_seg), _stream()))
     return bits, counts
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# interleaved row blocks: the simple coder, one CDF row per symbol (one wave per chunk; INTEGRATION.md, "Interleaved row blocks")
+
+def rans_rows_il_encode_dev(start: torch.Tensor, freq_m1: torch.Tensor, width: int, seg_edges: Sequence[int],
+                            ab: Optional[Tuple[int, int]] = None):
+    """start, freq_m1 int16 [n] (uint16 bits) on the device, as logits_to_ranges / pmf_to_ranges_f32 write them; width: the row width c
+    the decoder will search (header only); seg_edges: host list [n_seg + 1] of symbol offsets, one block per segment
+    [seg_edges[s], seg_edges[s + 1]) -- every (level, cloud) pair of a frame can be a segment of ONE call; ab = (a, b) for every
+    segment, None: the default policy per segment.
+    -> (out uint8 [worst case], meta int64 [n_seg + 1], offsets): block s is out[offsets[s]: offsets[s] + meta[s]], meta[n_seg] is the
+    status word (non-zero: a range that leaves [0, 65536], the blocks are void).  Nothing is synchronised: `meta` is read after the
+    caller's own copy / synchronise."""
+    from .rans_coder import InterleavedRowCoder
+    edges = [int(e) for e in seg_edges]
+    n_seg = len(edges) - 1
+    n = start.numel()
+    if n_seg < 1 or edges[0] < 0 or edges[-1] > n or any(b < a for a, b in zip(edges[:-1], edges[1:])) or freq_m1.numel() != n:
+        raise ValueError('seg_edges must rise inside [0, n], one (start, freq - 1) pair per symbol')
+    if not 2 <= int(width) <= 256:
+        raise ValueError('row width in 2..256 expected')
+    for a, b in [ab] if ab is not None else []:
+        if not (0 <= int(a) <= 6 and 4 <= int(b) <= 12):
+            raise ValueError('a in 0..6 and b in 4..12 expected')
+    abs_ = [ab if ab is not None else InterleavedRowCoder.policy(e1 - e0) for e0, e1 in zip(edges[:-1], edges[1:])]
+    dev = start.device
+    table = torch.tensor(edges + [int(a) | int(b) << 8 for a, b in abs_], dtype=torch.int64, pin_memory=True)
+    offsets = torch.zeros(n_seg + 1, dtype=torch.int64)
+    L = lib()
+    need = _ok(L.fpcc_rans_rows_il_encode_dev(None, None, int(width), table.data_ptr(), None, n_seg, None, 0, None, None, offsets.data_ptr(),
+                                              None, 0, None))
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+    offsets = offsets.tolist()
+    out = torch.empty(max(offsets[-1], 16), dtype=torch.uint8, device=dev)
+    meta = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    table_d = table.to(dev, non_blocking=True)
+    _ok(L.fpcc_rans_rows_il_encode_dev(_dev(start, torch.int16, 'start', n == 0), _dev(freq_m1, torch.int16, 'freq_m1', n == 0), int(width),
+                                       table.data_ptr(), table_d.data_ptr(), n_seg, out.data_ptr(), out.numel(), meta.data_ptr(),
+                                       meta.data_ptr() + 8 * n_seg, None, ws.data_ptr(), int(need), _stream()))
+    return out, meta, offsets
+
+
+def rans_rows_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, rows: torch.Tensor, n_seg: int,
+                            symbols_out: Optional[torch.Tensor] = None):
+    """blocks uint8 [bytes] and chunks int64 [n_chunks, 6] on the device (the descriptors rans_coder.InterleavedRowCoder.chunk_table
+    builds from validated headers), rows int16 [n, c] (uint16 bits, as logits_to_cdf16 writes them; they stay where they are)
+    -> (symbols int16 [n], counts int32 [n_seg + 1]: per segment sum popcount(symbol + 1), the children of an octree level, then the
+    sticky status word, 0 = fine), all on the device; nothing is synchronised.  symbols_out: an int16 [n] tensor to decode into"""
+    if rows.dim() != 2 or not 2 <= rows.shape[1] <= 256:
+        raise ValueError('rows must be [n, c] with c in 2..256')
+    n, c = rows.shape
+    dev = rows.device
+    if chunks.dim() != 2 or chunks.shape[1] != 6 or n_seg < 1:
+        raise ValueError('chunks must be [n_chunks, 6], n_seg >= 1')
+    sym = torch.empty(n, dtype=torch.int16, device=dev) if symbols_out is None else symbols_out
+    if sym.numel() != n:
+        raise ValueError('symbols_out must hold one symbol per row')
+    _dev(sym, torch.int16, 'symbols_out', n == 0)
+    counts = torch.zeros(n_seg + 1, dtype=torch.int32, device=dev)
+    n_chunks = chunks.shape[0]
+    _ok(lib().fpcc_rans_rows_il_decode_dev(_dev(blocks, torch.uint8, 'blocks', n_chunks == 0), blocks.numel() if blocks is not None else 0,
+                                           _dev(chunks, torch.int64, 'chunks', n_chunks == 0), n_chunks,
+                                           _dev(rows, torch.int16, 'rows', n_chunks == 0), n, int(c), sym.data_ptr(), counts.data_ptr(),
+                                           int(n_seg), counts.data_ptr() + 4 * int(n_seg), _stream()))
+    return sym, counts

@@ -242,6 +242,116 @@ class InterleavedBinaryCoder:
         return out
 
 
+class InterleavedRowCoder:
+    """The simple coder (one CDF row per symbol) with 2^a interleaved states: one block per call ("Interleaved row
+    blocks").  The host pair of libfpcc_host; the device pair is hipops.rans_rows_il_encode_dev / rans_rows_il_decode_dev -- same
+    bytes.  Chunk geometry and default policy are InterleavedBinaryCoder's."""
+    TAG = 0xB0
+    HEADER = 8
+    policy = staticmethod(InterleavedBinaryCoder.policy)
+    n_chunks = staticmethod(InterleavedBinaryCoder.n_chunks)
+
+    @classmethod
+    def worst_case_bytes(cls, n: int, a: int, b: int) -> int:
+        """header + lengths + per chunk the initial states and two bytes per symbol (a symbol emits at most two: freq >= 1)"""
+        k = cls.n_chunks(n, a, b)
+        return cls.HEADER + 4 * k + 4 * (1 << a) * k + 2 * n
+
+    @classmethod
+    def parse_header(cls, block, n: int, c: int) -> Tuple[int, int, List[int]]:
+        """(a, b, chunk payload lengths) of a block that codes n symbols under rows of width c; ValueError for anything a decoder must
+        not be started on"""
+        block = memoryview(block)
+        if len(block) < cls.HEADER:
+            raise ValueError('interleaved row block: shorter than its header')
+        if block[0] & 0xF8 != cls.TAG:
+            raise ValueError('interleaved row block: wrong tag byte')
+        a, b = block[0] & 7, block[1]
+        if a > 6 or not 4 <= b <= 12:
+            raise ValueError('interleaved row block: lanes = 2^a with a in 0..6 and symbols per lane = 2^b with b in 4..12')
+        if int.from_bytes(block[2:6], 'little') != n:
+            raise ValueError('interleaved row block: codes another number of symbols than the level has voxels')
+        if not 2 <= c <= 256 or int.from_bytes(block[6:8], 'little') != c:
+            raise ValueError('interleaved row block: coded under rows of another width (2..256)')
+        k = cls.n_chunks(n, a, b)
+        if len(block) < cls.HEADER + 4 * k:
+            raise ValueError('interleaved row block: shorter than its table of chunk lengths')
+        lens = np.frombuffer(block[cls.HEADER:cls.HEADER + 4 * k], dtype='<u4').astype(np.int64).tolist()
+        if any(v < 4 << a for v in lens):
+            raise ValueError('interleaved row block: a chunk shorter than its initial states')
+        if sum(lens) != len(block) - cls.HEADER - 4 * k:
+            raise ValueError('interleaved row block: chunk lengths do not sum to the payload')
+        return a, b, lens
+
+    @classmethod
+    def chunk_table(cls, block, n: int, c: int, block_at: int, sym0: int, seg: int) -> np.ndarray:
+        """int64 [K, 6] descriptors of a VALIDATED block for fpcc_rans_rows_il_decode_dev: the block lies at byte `block_at` of the
+        device buffer and codes symbols [sym0, sym0 + n) of segment `seg`"""
+        a, b, lens = cls.parse_header(block, n, c)
+        k = len(lens)
+        out = np.empty((k, 6), dtype=np.int64)
+        lens = np.asarray(lens, dtype=np.int64)
+        out[:, 0] = block_at + cls.HEADER + 4 * k + np.cumsum(lens) - lens
+        out[:, 1] = lens
+        out[:, 2] = sym0 + (np.arange(k, dtype=np.int64) << (a + b))
+        out[:, 3] = np.minimum(1 << (a + b), n - (np.arange(k, dtype=np.int64) << (a + b)))
+        out[:, 4] = seg
+        out[:, 5] = a
+        return out
+
+    @staticmethod
+    def ranges_of(rows: np.ndarray, symbols: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """(start, freq) int64 [n] of symbols under rows uint16 [n, c] (entry s = upper edge of symbol s, the last edge 65536)"""
+        rows = np.asarray(rows, dtype=np.uint16)
+        sym = np.asarray(symbols).reshape(-1).astype(np.int64)
+        n, c = rows.shape
+        if sym.size != n or (n and (sym.min() < 0 or sym.max() >= c)):
+            raise ValueError('one symbol in [0, c) per row expected')
+        at = np.arange(n)
+        wide = rows.astype(np.int64)
+        lo = np.where(sym > 0, wide[at, np.maximum(sym - 1, 0)], 0)
+        hi = np.where(sym == c - 1, 65536, wide[at, sym])
+        return lo, hi - lo
+
+    def encode(self, start: np.ndarray, freq: np.ndarray, c: int, a: Optional[int] = None, b: Optional[int] = None) -> bytes:
+        """symbol i has the range [start[i], start[i] + freq[i]) out of 65536; c: the width of the rows the decoder searches"""
+        start = np.asarray(start).reshape(-1).astype(np.int64)
+        freq = np.asarray(freq).reshape(-1).astype(np.int64)
+        if start.shape != freq.shape:
+            raise ValueError('one range per symbol expected')
+        n = start.size
+        pa, pb = self.policy(n)
+        a, b = pa if a is None else int(a), pb if b is None else int(b)
+        if not (0 <= a <= 6 and 4 <= b <= 12 and 2 <= int(c) <= 256):
+            raise ValueError('a in 0..6, b in 4..12 and c in 2..256 expected')
+        if n and int(freq.min()) <= 0:
+            raise ValueError('a zero frequency cannot be coded')
+        if n and (int(start.min()) < 0 or int((start + freq).max()) > 65536):
+            raise ValueError('a range must lie inside [0, 65536]')
+        cap = self.worst_case_bytes(n, a, b)
+        buf = np.empty(cap, dtype=np.uint8)
+        s16, f16 = np.ascontiguousarray(start.astype(np.uint16)), np.ascontiguousarray((freq - 1).astype(np.uint16))
+        got = host_check(host().fpcc_rans_rows_il_encode(_p(s16), _p(f16), n, int(c), a, b, _p(buf), cap))
+        return buf[:got].tobytes()
+
+    def encode_rows(self, rows: np.ndarray, symbols: np.ndarray, a: Optional[int] = None, b: Optional[int] = None) -> bytes:
+        rows = np.asarray(rows, dtype=np.uint16)
+        start, freq = self.ranges_of(rows, symbols)
+        return self.encode(start, freq, rows.shape[1], a, b)
+
+    def decode(self, block: bytes, rows: np.ndarray) -> np.ndarray:
+        """rows uint16 [n, c] -> uint16 [n] symbols"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint16)
+        n, c = rows.shape
+        self.parse_header(block, n, c)
+        data = np.frombuffer(block, dtype=np.uint8)
+        out = np.empty(n, dtype=np.uint16)
+        code = host().fpcc_rans_rows_il_decode(_p(data), data.size, _p(rows), n, c, _p(out))
+        if code < 0:
+            raise ValueError('interleaved row block: ' + host().fpcc_host_strerror(code).decode())
+        return out
+
+
 class RansEncoder:
     def __init__(self, enc_buf_size: int = 32 << 20):
         self._cap = int(enc_buf_size)

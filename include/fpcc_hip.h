@@ -935,6 +935,30 @@ int fpcc_rans_binary_il_decode_dev(const uint8_t *blocks, int64_t blocks_bytes, 
                                    const uint16_t *prob1, int64_t n, uint8_t *bits_out, int32_t *ones_out, int32_t n_seg,
                                    int32_t *status, void *stream);
 
+/* Interleaved row blocks (rans_rows_il.hip): the opt-in occupancy block format of the integer codec ("Interleaved row
+ * blocks"), byte for byte what fpcc_rans_rows_il_encode / _decode of libfpcc_host write and read: the chunk geometry of the binary
+ * blocks above with the simple coder's step (a range out of 2^16 per symbol, found by the decoder in the symbol's own CDF row).  One
+ * wave codes one chunk; the chunks of all segments -- every (level, cloud) pair of a frame when encoding, the clouds of one level when
+ * decoding -- are one launch.  Neither call synchronises or reads anything back.  Segment table and workspace: as for
+ * fpcc_rans_binary_il_encode_dev.
+ * encode: start / freq_m1 uint16 [symbols] as fpcc_logits_to_ranges / fpcc_pmf_to_ranges_f32 write them; width (2..256) is the row
+ *   width c the decoder will search (header only).  Block s is written contiguously at out + block_off_host[s] (worst-case offsets,
+ *   n_seg + 1 of them, filled on every call that has the pointer, the size query included) and len_out[s] (device int64) receives its
+ *   length.  *status (device, zeroed by the caller) gets bit 0 when a range ends past 65536: the blocks are then void. */
+int64_t fpcc_rans_rows_il_encode_dev(const uint16_t *start, const uint16_t *freq_m1, int32_t width, const int64_t *seg_host,
+                                     const int64_t *seg, int32_t n_seg, uint8_t *out, int64_t out_bytes, int64_t *len_out,
+                                     int32_t *status, int64_t *block_off_host, void *ws, int64_t ws_bytes, void *stream);
+/* decode: chunks int64 [n_chunks][6] = {byte offset of the chunk's payload in blocks, payload length, first symbol, symbols, segment,
+ *   a}, built by the HOST from validated headers; every descriptor is checked against blocks_bytes, n and n_seg before an address is
+ *   formed.  rows uint16 [n][width] stay in device memory where fpcc_logits_to_cdf16 wrote them (2-byte aligned); a round's rows are
+ *   staged into LDS one round ahead.  symbols_out int16 [n]; children_out int32 [n_seg] (zeroed by the caller) gets per segment the sum
+ *   of popcount(symbol + 1); *status (zeroed by the caller) is sticky: bit 0 an initial state below 2^23, bit 1 a row that does not
+ *   increase at the decoded symbol, bit 2 a chunk read past its payload (zeros were shifted in), bit 3 a descriptor outside the
+ *   buffers (that chunk is skipped). */
+int fpcc_rans_rows_il_decode_dev(const uint8_t *blocks, int64_t blocks_bytes, const int64_t *chunks, int64_t n_chunks,
+                                 const uint16_t *rows, int64_t n, int32_t width, int16_t *symbols_out, int32_t *children_out,
+                                 int32_t n_seg, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------ */
 /* Mixed-precision TRAINING: bfloat16 operands, fp32 accumulation (conv_bf16.hip).  Never used by inference.       */
 /* ------------------------------------------------------------------------------------------------------------ */

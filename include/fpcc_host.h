@@ -132,6 +132,22 @@ int64_t fpcc_simple_dec_pop(fpcc_simple_dec *, const uint16_t *rows, int64_t n_r
 int64_t fpcc_simple_dec_tell(const fpcc_simple_dec *d, uint32_t *state_out, int64_t *position_out);
 int64_t fpcc_simple_dec_pop_bin(fpcc_simple_dec *, const uint16_t *edge, int64_t n_rows, uint8_t *bits_out, int64_t n);
 
+/* The simple coder with 2^a interleaved states: the opt-in occupancy block format of the integer codec ("Interleaved
+ * row blocks"; no counterpart in the reference).  Chunks, lanes, rounds and payload order are fpcc_rans_binary_il_*'s, the per-lane
+ * step is fpcc_simple_enc_push_ranges' / fpcc_simple_dec_pop's.  Host statement of the format and oracle of fpcc_rans_rows_il_*_dev.
+ * encode: symbol i has the range [start[i], start[i] + freq_m1[i] + 1) out of 2^16 (what fpcc_logits_to_ranges writes); c in 2..256 is
+ *         the width of the rows the decoder will search (header only); a in 0..6 and b in 4..12, or -1 for the default policy.  Writes
+ *         the block at the START of out[0..cap) and returns its length; a range that ends past 65536 is FPCC_HOST_E_ARG (a zero
+ *         frequency has no representation here), a block that does not fit FPCC_HOST_E_BUFFER.
+ * decode: rows uint16 [n][c] as fpcc_logits_to_cdf16 writes them (entry s = upper edge of symbol s, the last edge implicitly 65536);
+ *         n and c are what the caller expects.  Validated before a payload byte is read: tag, a, b, n, c, every chunk length >= 4 *
+ *         lanes, lengths summing to the rest of the block; then every initial state (>= 2^23), and while decoding that the row
+ *         increases at the decoded symbol: FPCC_HOST_E_ARG otherwise.  Bytes past a chunk's payload read as zero. */
+int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1, int64_t n, int c, int a, int b, uint8_t *out,
+                                 int64_t cap);
+int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *rows, int64_t n, int c,
+                                 uint16_t *symbols_out);
+
 #ifdef __cplusplus
 }
 #endif
