@@ -1,69 +1,19 @@
 // Interleaved binary rANS blocks on the device: the opt-in occupancy format of INTEGRATION.md ("Interleaved occupancy blocks").
 //
-// The per-lane arithmetic is k_rans_binary_decode's (rans_dev.hip) and libfpcc_host's binary coder: 32-bit state, L = 2^23, byte
-// renormalisation, 16-bit prob1.  What the format adds is 2^a states per chunk that share one byte stream, so a chunk is the work of
-// ONE wave -- lane l owns state l -- and the chunks of a level (of all its clouds) are independent waves of one launch:
-//   * a round codes symbols [r * lanes, (r + 1) * lanes) of the chunk: lane l loads prob1 / bits of element r * lanes + l (coalesced);
-//   * who takes / gives a byte in a refill step is a ballot, where in the stream is the count of set bits below the lane (v_mbcnt);
-//     a step in which no lane moves a byte is skipped on a wave-uniform branch;
-//   * the decoder reads its refill bytes from a 4-KB window of the payload in LDS, filled 64 bytes per lane at a time, so no global
-//     load sits on the state's dependency chain; the encoder's bytes leave as plain byte stores into the chunk's worst-case slot.
+// The container's constants, segment-table geometry, compaction kernel and encode entry are rans_il_common.h's, and the wave protocol
+// is described there.  The two coder kernels are this file's: every shared piece tried in them measured slower or took more registers
+// (profiles/interleaved_shared.md).
+// The per-lane arithmetic is k_rans_binary_decode's (rans_dev.hip) and libfpcc_host's binary coder: 16-bit prob1, a one is the range
+// [65536 - prob1, 65536), a zero [0, 65536 - prob1).  In a round lane l loads prob1 / bits of element r * lanes + l (coalesced).
 // Host twin and oracle: fpcc_rans_binary_il_encode / _decode (csrc/host/rans_host.cpp) -- same bytes.
-#include "common.h"
+#include "rans_il_common.h"
 
 namespace fpcc {
 namespace {
 
-constexpr uint32_t kLow = 1u << 23;
 constexpr uint32_t kOne = 1u << 16;
-constexpr int kWindow = 4096;              // bytes of payload held in LDS by the decoder
-constexpr int kRoundMax = 3 * 64;          // bytes one round can consume: 3 refill steps of 64 lanes
 constexpr int kBatch = 8;                  // rounds whose operands are requested together
 static_assert(kBatch * kRoundMax + 256 + 4 <= kWindow, "the window holds the initial states or what a batch of rounds can consume");
-constexpr uint32_t kNone = 0xffffffffu;    // "this lane has no symbol in that round" in a batch of operands
-
-__device__ __forceinline__ int lanes_below(unsigned long long mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
-// Segment table (int64, device and host copies alike): [0 .. n_seg] symbol offsets of the segments, then n_seg words a | b << 8.
-// A chunk never spans a segment: segment s has ceil(n_s / 2^(a + b)) chunks, numbered segment-major.
-struct ChunkOfSegment {
-    int seg, a, b;
-    int64_t k;             // chunk index inside the segment
-    int64_t chunks;        // chunks of the segment
-    int64_t sym0, m;       // first symbol (global index) and number of symbols of the chunk
-    int64_t slot;          // byte offset of the chunk's slot in the workspace
-    int64_t first_chunk;   // global index of the segment's first chunk
-};
-
-__host__ __device__ inline int64_t slot_full(int a, int b) { return ((int64_t)4 << a) + ((int64_t)2 << (a + b)); }
-__host__ __device__ inline int64_t chunks_of(int64_t n, int a, int b) { return (n + ((int64_t)1 << (a + b)) - 1) >> (a + b); }
-// worst case of a block: header, lengths, per chunk the states and two bytes per symbol
-__host__ __device__ inline int64_t block_cap(int64_t n, int a, int b) {
-    const int64_t k = chunks_of(n, a, b);
-    return 6 + 4 * k + ((int64_t)4 << a) * k + 2 * n;
-}
-
-__host__ __device__ inline bool find_chunk(const int64_t *seg, int n_seg, int64_t chunk, ChunkOfSegment &c) {
-    int64_t first = 0, slot = 0;
-    for (int s = 0; s < n_seg; ++s) {
-        const int a = (int)(seg[n_seg + 1 + s] & 0xff), b = (int)((seg[n_seg + 1 + s] >> 8) & 0xff);
-        const int64_t n = seg[s + 1] - seg[s];
-        const int64_t chunks = chunks_of(n, a, b);
-        if (chunk < first + chunks) {
-            c.seg = s; c.a = a; c.b = b; c.k = chunk - first; c.chunks = chunks; c.first_chunk = first;
-            c.sym0 = seg[s] + (c.k << (a + b));
-            const int64_t left = seg[s + 1] - c.sym0;
-            c.m = left < ((int64_t)1 << (a + b)) ? left : ((int64_t)1 << (a + b));
-            c.slot = slot + c.k * slot_full(a, b);
-            return true;
-        }
-        first += chunks;
-        slot += chunks * slot_full(a, b);
-    }
-    return false;
-}
 
 // ---- encoder ------------------------------------------------------------------------------------------------------------------
 // one wave per chunk: the rounds run backwards, the payload grows down from the end of the chunk's slot
@@ -144,70 +94,6 @@ __global__ __launch_bounds__(64) void k_il_encode(const uint8_t *__restrict__ bi
     }
     if (__ballot(bad) && lane == 0) atomicOr(status, 1);
     if (lane == 0) chunk_len[blockIdx.x] = (int32_t)(slot_bytes - wp);
-}
-
-// one row of blocks per segment (blockIdx.x), blockIdx.y stripes the bytes: header, chunk lengths, then the chunks' payloads moved
-// from the ends of their slots into one contiguous block at out + off[seg]; len_out[seg] = block length
-__global__ __launch_bounds__(256) void k_il_compact(const int64_t *__restrict__ seg, int n_seg, const uint8_t *__restrict__ slots,
-                                                    const int32_t *__restrict__ chunk_len, int64_t *__restrict__ chunk_dst,
-                                                    uint8_t *__restrict__ out, int64_t *__restrict__ len_out) {
-    __shared__ int64_t scan[256];
-    __shared__ int64_t carry;
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int a = (int)(seg[n_seg + 1 + s] & 0xff), b = (int)((seg[n_seg + 1 + s] >> 8) & 0xff);
-    const int64_t n = seg[s + 1] - seg[s];
-    const int64_t chunks = chunks_of(n, a, b);
-    int64_t first = 0, slot0 = 0, dst0 = 0;
-    for (int t = 0; t < s; ++t) {
-        const int ta = (int)(seg[n_seg + 1 + t] & 0xff), tb = (int)((seg[n_seg + 1 + t] >> 8) & 0xff);
-        const int64_t tn = seg[t + 1] - seg[t];
-        first += chunks_of(tn, ta, tb);
-        slot0 += chunks_of(tn, ta, tb) * slot_full(ta, tb);
-        dst0 += block_cap(tn, ta, tb);
-    }
-    uint8_t *block = out + dst0;
-    // exclusive scan of the segment's chunk lengths, 256 at a time (every blockIdx.y computes and writes the same values)
-    if (tid == 0) carry = 6 + 4 * chunks;
-    __syncthreads();
-    for (int64_t k0 = 0; k0 < chunks; k0 += 256) {
-        const int64_t k = k0 + tid;
-        const int64_t mine = k < chunks ? chunk_len[first + k] : 0;
-        scan[tid] = mine;
-        __syncthreads();
-        for (int d = 1; d < 256; d <<= 1) {
-            const int64_t add = tid >= d ? scan[tid - d] : 0;
-            __syncthreads();
-            scan[tid] += add;
-            __syncthreads();
-        }
-        if (k < chunks) chunk_dst[first + k] = carry + scan[tid] - mine;
-        __syncthreads();
-        if (tid == 0) carry += scan[255];
-        __syncthreads();
-    }
-    if (blockIdx.y == 0) {
-        if (tid == 0) {
-            block[0] = (uint8_t)(0xA0 | a);
-            block[1] = (uint8_t)b;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) block[2 + i] = (uint8_t)((uint64_t)n >> (8 * i));
-            len_out[s] = carry;
-        }
-        for (int64_t k = tid; k < chunks; k += 256) {
-            const uint32_t len = (uint32_t)chunk_len[first + k];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) block[6 + 4 * k + i] = (uint8_t)(len >> (8 * i));
-        }
-    }
-    const int64_t per = (int64_t)1 << (a + b);
-    for (int64_t k = 0; k < chunks; ++k) {
-        const int64_t len = chunk_len[first + k];
-        const int64_t left = n - k * per;
-        const int64_t slot_bytes = ((int64_t)4 << a) + 2 * (left < per ? left : per);
-        const uint8_t *src = slots + slot0 + k * slot_full(a, b) + slot_bytes - len;
-        uint8_t *dst = block + chunk_dst[first + k];
-        for (int64_t i = (int64_t)blockIdx.y * 256 + tid; i < len; i += (int64_t)gridDim.y * 256) dst[i] = src[i];
-    }
 }
 
 // ---- decoder ------------------------------------------------------------------------------------------------------------------
@@ -344,46 +230,17 @@ using namespace fpcc;
 extern "C" int64_t fpcc_rans_binary_il_encode_dev(const uint8_t *bits, const uint16_t *prob1, const int64_t *seg_host, const int64_t *seg,
                                                   int32_t n_seg, uint8_t *out, int64_t out_bytes, int64_t *len_out, int32_t *status,
                                                   int64_t *block_off_host, void *ws, int64_t ws_bytes, void *stream) {
-    if (!seg_host || n_seg < 1) return fail_arg("rans_binary_il_encode_dev: a host copy of the segment table with n_seg >= 1 is required");
-    int64_t chunks = 0, slots = 0, cap = 0;
-    for (int s = 0; s < n_seg; ++s) {
-        const int a = (int)(seg_host[n_seg + 1 + s] & 0xff), b = (int)((seg_host[n_seg + 1 + s] >> 8) & 0xff);
-        const int64_t n = seg_host[s + 1] - seg_host[s];
-        if (a > 6 || b < 4 || b > 12 || (seg_host[n_seg + 1 + s] >> 16) != 0 || n < 0 || n > (int64_t)UINT32_MAX || seg_host[0] < 0)
-            return fail_arg("rans_binary_il_encode_dev: a in 0..6, b in 4..12, segments that do not decrease, at most 2^32 - 1 symbols each");
-        if (block_off_host) block_off_host[s] = cap;
-        chunks += chunks_of(n, a, b);
-        slots += chunks_of(n, a, b) * slot_full(a, b);
-        cap += block_cap(n, a, b);
-    }
-    if (block_off_host) block_off_host[n_seg] = cap;
-    if (chunks > 0x7fffffff) return fail_arg("rans_binary_il_encode_dev: too many chunks for one launch");
-    // workspace: the chunks' slots | int64 destination per chunk | int32 length per chunk
-    const int64_t dst_at = align_up(slots, 16), len_at = dst_at + 8 * chunks, need = len_at + 4 * chunks;
-    if (!ws) return need;
-    if (ws_bytes < need) { set_error("rans_binary_il_encode_dev: workspace of %lld bytes, %lld needed", (long long)ws_bytes, (long long)need); return FPCC_E_WORKSPACE; }
-    if (out_bytes < cap) return fail_arg("rans_binary_il_encode_dev: out is smaller than the worst case of its blocks");
-    if (!seg || !out || !len_out || !status || (seg_host[n_seg] > 0 && (!bits || !prob1))) return fail_arg("rans_binary_il_encode_dev: null pointer");
-    uint8_t *base = static_cast<uint8_t *>(ws);
-    int32_t *chunk_len = reinterpret_cast<int32_t *>(base + len_at);
-    int64_t *chunk_dst = reinterpret_cast<int64_t *>(base + dst_at);
-    if (chunks > 0) {
-        hipLaunchKernelGGL(k_il_encode, dim3((unsigned)chunks), dim3(64), 0, as_stream(stream), bits, prob1, seg, (int)n_seg, base, chunk_len,
-                           status);
-        FPCC_LAUNCHED(k_il_encode);
-    }
-    // stripes over the bytes: enough blocks that a 1 M-voxel level's ~100 KB moves in a few microseconds, few enough to stay one wave of blocks
-    const unsigned stripes = n_seg >= 16 ? 2 : 16;
-    hipLaunchKernelGGL(k_il_compact, dim3((unsigned)n_seg, stripes), dim3(256), 0, as_stream(stream), seg, (int)n_seg, base, chunk_len, chunk_dst,
-                       out, len_out);
-    FPCC_LAUNCHED(k_il_compact);
-    return FPCC_OK;
+    return encode_blocks<0xA0, 6>("rans_binary_il_encode_dev", bits && prob1, 0, seg_host, seg, n_seg, out, out_bytes, len_out, status,
+                                  block_off_host, ws, ws_bytes, stream, [&](unsigned chunks, uint8_t *slots, int32_t *chunk_len) {
+                                      hipLaunchKernelGGL(k_il_encode, dim3(chunks), dim3(64), 0, as_stream(stream), bits, prob1, seg, (int)n_seg,
+                                                         slots, chunk_len, status);
+                                  });
 }
 
 extern "C" int fpcc_rans_binary_il_decode_dev(const uint8_t *blocks, int64_t blocks_bytes, const int64_t *chunks, int64_t n_chunks,
                                               const uint16_t *prob1, int64_t n, uint8_t *bits_out, int32_t *ones_out, int32_t n_seg,
                                               int32_t *status, void *stream) {
-    if (n < 0 || n_chunks < 0 || n_chunks > 0x7fffffff || blocks_bytes < 0 || n_seg < 1) return fail_arg("rans_binary_il_decode_dev: bad sizes");
+    if (!decode_sizes_ok(n, n_chunks, blocks_bytes, n_seg)) return fail_arg("rans_binary_il_decode_dev: bad sizes");
     if (n_chunks == 0) return FPCC_OK;
     if (!blocks || !chunks || !prob1 || !bits_out || !ones_out || !status) return fail_arg("rans_binary_il_decode_dev: null pointer");
     hipLaunchKernelGGL(k_il_decode, dim3((unsigned)n_chunks), dim3(64), 0, as_stream(stream), blocks, blocks_bytes, chunks, prob1, n, bits_out,

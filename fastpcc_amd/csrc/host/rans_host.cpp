@@ -325,158 +325,9 @@ int64_t binary_encode(const uint8_t *bits, const uint16_t *p1, int64_t n, uint8_
     return w.finish();
 }
 
-// ---- interleaved binary blocks ("Interleaved occupancy blocks") -------------------------------------------------
-// The per-lane arithmetic is binary_encode's / fpcc_rans_binary_decode's; what differs is that 2^a states share one byte stream.
-// These two are the plain statement of the format (the device kernels of csrc/hip/rans_il.hip are checked against them), not a hot path.
-constexpr int kIlMaxLanes = 64;
-
-struct IlHeader {
-    int a = 0, b = 0;
-    int64_t n = 0, chunks = 0, per_chunk = 0;      // per_chunk = lanes * 2^b symbols
-    int lanes() const { return 1 << a; }
-};
-
-inline uint32_t load_le32(const uint8_t *p) { return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24; }
-inline void store_le32(uint8_t *p, uint32_t v) {
-    p[0] = static_cast<uint8_t>(v); p[1] = static_cast<uint8_t>(v >> 8); p[2] = static_cast<uint8_t>(v >> 16); p[3] = static_cast<uint8_t>(v >> 24);
-}
-
-// the encoder's default policy: 1024 symbols per lane and chunk, 64 lanes from 16384 symbols on, below that the largest power of two
-// that leaves a lane 256 symbols
-inline void il_policy(int64_t n, int &a, int &b) {
-    if (b == -1) b = 10;
-    if (a == -1) {
-        a = 6;
-        if (n < 16384) for (a = 0; (int64_t(2) << a) <= std::max<int64_t>(1, n / 256); ++a) {}
-    }
-}
-
-inline bool il_geometry(int a, int b, int64_t n, IlHeader &h) {
-    if (a < 0 || a > 6 || b < 4 || b > 12 || n < 0 || n > int64_t(UINT32_MAX)) return false;
-    h.a = a; h.b = b; h.n = n;
-    h.per_chunk = int64_t(1) << (a + b);
-    h.chunks = (n + h.per_chunk - 1) / h.per_chunk;
-    return true;
-}
-
-// one chunk of m symbols into the END of slot[0 .. 4 lanes + 2 m); returns the payload length or a negative code
-int64_t il_encode_chunk(const uint8_t *bits, const uint16_t *p1, int64_t m, int lanes, uint8_t *slot, int64_t slot_bytes) {
-    uint32_t x[kIlMaxLanes];
-    for (int l = 0; l < lanes; ++l) x[l] = kLow;
-    int64_t wp = slot_bytes;
-    const int64_t rounds = (m + lanes - 1) / lanes;
-    for (int64_t r = rounds - 1; r >= 0; --r) {
-        const int active = static_cast<int>(std::min<int64_t>(lanes, m - r * lanes));
-        uint8_t first[kIlMaxLanes], second[kIlMaxLanes];       // what the decoder takes in refill step 0 / step 1
-        int k_of[kIlMaxLanes], c1 = 0, c2 = 0;
-        for (int l = 0; l < active; ++l) {
-            const int64_t j = r * lanes + l;
-            const uint32_t p = p1[j];
-            if (p == 0) return FPCC_HOST_E_ARG;
-            const bool one = bits[j] != 0;
-            const uint32_t freq = one ? p : kProbOne - p, start = one ? kProbOne - p : 0u;
-            const uint32_t ceiling = ((kLow >> kProbBits) << 8) * freq;
-            uint32_t v = x[l];
-            uint8_t e[2] = {0, 0};
-            int k = 0;
-            while (v >= ceiling) { e[k++] = static_cast<uint8_t>(v); v >>= 8; }      // at most twice: v < 2^31, ceiling >= 2^15
-            x[l] = ((v / freq) << kProbBits) + v % freq + start;
-            k_of[l] = k;
-            first[l] = k ? e[k - 1] : 0;                           // the decoder reads a lane's bytes of a round last-emitted first
-            second[l] = e[0];
-            c1 += k >= 1;
-            c2 += k >= 2;
-        }
-        wp -= c1 + c2;
-        int64_t at1 = wp, at2 = wp + c1;
-        for (int l = 0; l < active; ++l) {
-            if (k_of[l] >= 1) slot[at1++] = first[l];
-            if (k_of[l] >= 2) slot[at2++] = second[l];
-        }
-    }
-    wp -= 4 * lanes;
-    for (int l = 0; l < lanes; ++l) store_le32(slot + wp + 4 * l, x[l]);
-    return slot_bytes - wp;
-}
-
 }  // namespace
 
 extern "C" {
-
-int64_t fpcc_rans_binary_il_encode(const uint8_t *bits, const uint16_t *prob1, int64_t n, int a, int b, uint8_t *out, int64_t cap) {
-    if (!out || n < 0 || cap < 0 || (n > 0 && (!bits || !prob1))) return FPCC_HOST_E_ARG;
-    il_policy(n, a, b);
-    IlHeader h;
-    if (!il_geometry(a, b, n, h)) return FPCC_HOST_E_ARG;
-    const int lanes = h.lanes();
-    int64_t at = 6 + 4 * h.chunks;
-    if (cap < at) return FPCC_HOST_E_BUFFER;
-    out[0] = static_cast<uint8_t>(0xA0 | a);
-    out[1] = static_cast<uint8_t>(b);
-    store_le32(out + 2, static_cast<uint32_t>(n));
-    std::vector<uint8_t> slot(static_cast<size_t>(4 * lanes + 2 * h.per_chunk));
-    for (int64_t k = 0; k < h.chunks; ++k) {
-        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
-        const int64_t slot_bytes = 4 * lanes + 2 * m;
-        const int64_t len = il_encode_chunk(bits + s0, prob1 + s0, m, lanes, slot.data(), slot_bytes);
-        if (len < 0) return len;
-        if (cap - at < len) return FPCC_HOST_E_BUFFER;
-        std::memcpy(out + at, slot.data() + slot_bytes - len, static_cast<size_t>(len));
-        store_le32(out + 6 + 4 * k, static_cast<uint32_t>(len));
-        at += len;
-    }
-    return at;
-}
-
-int64_t fpcc_rans_binary_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *prob1, int64_t n, uint8_t *bits_out) {
-    if (!block || n < 0 || block_len < 6 || (n > 0 && (!prob1 || !bits_out))) return FPCC_HOST_E_ARG;
-    // the header, before a single payload byte is read: tag, a, b, the symbol count the caller expects, K, every length >= 4 lanes,
-    // the lengths summing to what is left of the block
-    if ((block[0] & 0xF8) != 0xA0) return FPCC_HOST_E_ARG;             // (0xA7, a = 7, passes this mask and fails il_geometry)
-    IlHeader h;
-    if (!il_geometry(block[0] & 7, block[1], n, h) || load_le32(block + 2) != static_cast<uint32_t>(n)) return FPCC_HOST_E_ARG;
-    const int lanes = h.lanes();
-    if (h.chunks > (block_len - 6) / 4) return FPCC_HOST_E_ARG;
-    int64_t rest = block_len - 6 - 4 * h.chunks;
-    for (int64_t k = 0; k < h.chunks; ++k) {
-        const int64_t len = load_le32(block + 6 + 4 * k);
-        if (len < 4 * lanes || len > rest) return FPCC_HOST_E_ARG;
-        rest -= len;
-    }
-    if (rest != 0) return FPCC_HOST_E_ARG;
-    const uint8_t *payload = block + 6 + 4 * h.chunks;
-    for (int64_t k = 0; k < h.chunks; ++k) {
-        const int64_t len = load_le32(block + 6 + 4 * k);
-        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
-        uint32_t x[kIlMaxLanes];
-        for (int l = 0; l < lanes; ++l) {
-            x[l] = load_le32(payload + 4 * l);
-            if (x[l] < kLow) return FPCC_HOST_E_ARG;                  // not a state any encoder flushes
-        }
-        int64_t pos = 4 * lanes;
-        const int64_t rounds = (m + lanes - 1) / lanes;
-        for (int64_t r = 0; r < rounds; ++r) {
-            const int active = static_cast<int>(std::min<int64_t>(lanes, m - r * lanes));
-            for (int l = 0; l < active; ++l) {
-                const int64_t j = s0 + r * lanes + l;
-                const uint32_t p = prob1[j], split = kProbOne - p;
-                const uint32_t slot = x[l] & (kProbOne - 1u), hi = x[l] >> kProbBits;
-                const bool one = slot >= split;
-                x[l] = one ? p * hi + (slot - split) : split * hi + slot;
-                bits_out[j] = static_cast<uint8_t>(one);
-            }
-            for (int t = 0; t < kMaxRefill; ++t)
-                for (int l = 0; l < active; ++l)
-                    if (x[l] < kLow) {
-                        const uint32_t byte = pos < len ? payload[pos] : 0u;      // past the chunk's payload: zeros, never another chunk's bytes
-                        ++pos;
-                        x[l] = (x[l] << 8) | byte;
-                    }
-        }
-        payload += len;
-    }
-    return FPCC_HOST_OK;
-}
 
 const char *fpcc_host_strerror(int64_t code) {
     switch (code) {
@@ -1105,25 +956,62 @@ int64_t fpcc_pool_wait(fpcc_pool *p) {
     return rc;
 }
 
-// ---- interleaved row blocks ("Interleaved row blocks") ----------------------------------------------------------
-// The binary block format's chunks, lanes, rounds and payload order with the SIMPLE coder's per-lane step (ranges out of 2^16 under
-// one CDF row per symbol: fpcc_simple_enc_push_ranges / fpcc_simple_dec_pop above).  A plain statement of the format -- the kernels of
-// csrc/hip/rans_rows_il.hip are checked against it -- not a hot path.
-int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1, int64_t n, int c, int a, int b, uint8_t *out,
-                                 int64_t cap) {
-    if (!out || n < 0 || cap < 0 || c < 2 || c > 256 || (n > 0 && (!start || !freq_m1))) return FPCC_HOST_E_ARG;
+}  // extern "C"
+
+// ---- interleaved blocks ("Interleaved occupancy blocks" and "Interleaved row blocks") ---------------------------------
+// One container for both: 2^a states share a chunk's byte stream, a block is header | chunk lengths | chunks.  The binary blocks
+// (tag 0xA0, 6-byte header) take a lane's step from binary_encode / fpcc_rans_binary_decode, the row blocks (tag 0xB0, 8-byte header
+// ending in the row width) from the SIMPLE coder (ranges out of 2^16 under one CDF row per symbol: fpcc_simple_enc_push_ranges /
+// fpcc_simple_dec_pop above).  These are the plain statement of the formats (the device kernels of csrc/hip/rans_il.hip and
+// rans_rows_il.hip are checked against them), not a hot path.
+namespace {
+
+constexpr int kIlMaxLanes = 64;
+
+struct IlHeader {
+    int a = 0, b = 0;
+    int64_t n = 0, chunks = 0, per_chunk = 0;      // per_chunk = lanes * 2^b symbols
+    int lanes() const { return 1 << a; }
+};
+
+inline uint32_t load_le32(const uint8_t *p) { return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24; }
+inline void store_le32(uint8_t *p, uint32_t v) {
+    p[0] = static_cast<uint8_t>(v); p[1] = static_cast<uint8_t>(v >> 8); p[2] = static_cast<uint8_t>(v >> 16); p[3] = static_cast<uint8_t>(v >> 24);
+}
+
+// the encoder's default policy: 1024 symbols per lane and chunk, 64 lanes from 16384 symbols on, below that the largest power of two
+// that leaves a lane 256 symbols
+inline void il_policy(int64_t n, int &a, int &b) {
+    if (b == -1) b = 10;
+    if (a == -1) {
+        a = 6;
+        if (n < 16384) for (a = 0; (int64_t(2) << a) <= std::max<int64_t>(1, n / 256); ++a) {}
+    }
+}
+
+inline bool il_geometry(int a, int b, int64_t n, IlHeader &h) {
+    if (a < 0 || a > 6 || b < 4 || b > 12 || n < 0 || n > int64_t(UINT32_MAX)) return false;
+    h.a = a; h.b = b; h.n = n;
+    h.per_chunk = int64_t(1) << (a + b);
+    h.chunks = (n + h.per_chunk - 1) / h.per_chunk;
+    return true;
+}
+
+// One block of n symbols into out: tag | a, b, n (bytes past 6 of a longer header are the caller's), the chunk lengths, the chunks.
+// range_of(j, lo, f) gives symbol j's range [lo, lo + f) out of 2^16, f >= 1, or false if the symbol cannot be coded.  Returns the
+// block length or a negative code.
+template <typename RangeOf>
+int64_t il_encode_block(int tag, int header, int64_t n, int a, int b, uint8_t *out, int64_t cap, RangeOf range_of) {
     il_policy(n, a, b);
     IlHeader h;
     if (!il_geometry(a, b, n, h)) return FPCC_HOST_E_ARG;
     const int lanes = h.lanes();
-    int64_t at = 8 + 4 * h.chunks;
+    int64_t at = header + 4 * h.chunks;
     if (cap < at) return FPCC_HOST_E_BUFFER;
-    out[0] = static_cast<uint8_t>(0xB0 | a);
+    out[0] = static_cast<uint8_t>(tag | a);
     out[1] = static_cast<uint8_t>(b);
     store_le32(out + 2, static_cast<uint32_t>(n));
-    out[6] = static_cast<uint8_t>(c);
-    out[7] = static_cast<uint8_t>(c >> 8);
-    std::vector<uint8_t> slot(static_cast<size_t>(4 * lanes + 2 * h.per_chunk));
+    std::vector<uint8_t> slot(static_cast<size_t>(4 * lanes + 2 * h.per_chunk));       // a chunk grows down from the end of its slot
     for (int64_t k = 0; k < h.chunks; ++k) {
         const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
         const int64_t slot_bytes = 4 * lanes + 2 * m;
@@ -1135,9 +1023,8 @@ int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1,
             uint8_t first[kIlMaxLanes], second[kIlMaxLanes];       // what the decoder takes in refill step 0 / step 1
             int k_of[kIlMaxLanes], c1 = 0, c2 = 0;
             for (int l = 0; l < active; ++l) {
-                const int64_t j = s0 + r * lanes + l;
-                const uint32_t lo = start[j], f = uint32_t(freq_m1[j]) + 1u;
-                if (lo + f > kProbOne) return FPCC_HOST_E_ARG;     // the range leaves the interval (f >= 1 by its representation)
+                uint32_t lo, f;
+                if (!range_of(s0 + r * lanes + l, lo, f)) return FPCC_HOST_E_ARG;
                 const uint32_t ceiling = ((kLow >> kProbBits) << 8) * f;
                 uint32_t v = x[l];
                 uint8_t e[2] = {0, 0};
@@ -1162,33 +1049,36 @@ int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1,
         const int64_t len = slot_bytes - wp;
         if (cap - at < len) return FPCC_HOST_E_BUFFER;
         std::memcpy(out + at, slot.data() + wp, static_cast<size_t>(len));
-        store_le32(out + 8 + 4 * k, static_cast<uint32_t>(len));
+        store_le32(out + header + 4 * k, static_cast<uint32_t>(len));
         at += len;
     }
     return at;
 }
 
-int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *rows, int64_t n, int c, uint16_t *symbols_out) {
-    if (!block || n < 0 || block_len < 8 || c < 2 || c > 256 || (n > 0 && (!rows || !symbols_out))) return FPCC_HOST_E_ARG;
-    // the header, before a single payload byte is read: tag, a, b, the symbol count and row width the caller expects, K, every length
-    // >= 4 lanes, the lengths summing to what is left of the block
-    if ((block[0] & 0xF8) != 0xB0) return FPCC_HOST_E_ARG;
-    IlHeader h;
-    if (!il_geometry(block[0] & 7, block[1], n, h) || load_le32(block + 2) != static_cast<uint32_t>(n)) return FPCC_HOST_E_ARG;
-    if ((int(block[6]) | int(block[7]) << 8) != c) return FPCC_HOST_E_ARG;
-    const int lanes = h.lanes();
-    if (h.chunks > (block_len - 8) / 4) return FPCC_HOST_E_ARG;
-    int64_t rest = block_len - 8 - 4 * h.chunks;
+// the header, before a single payload byte is read: tag, a, b, the symbol count the caller expects, K, every length >= 4 lanes, the
+// lengths summing to what is left of the block
+bool il_parse_header(const uint8_t *block, int64_t block_len, int tag, int header, int64_t n, IlHeader &h) {
+    if (block_len < header || (block[0] & 0xF8) != tag) return false;               // (a = 7 passes this mask and fails il_geometry)
+    if (!il_geometry(block[0] & 7, block[1], n, h) || load_le32(block + 2) != static_cast<uint32_t>(n)) return false;
+    if (h.chunks > (block_len - header) / 4) return false;
+    int64_t rest = block_len - header - 4 * h.chunks;
     for (int64_t k = 0; k < h.chunks; ++k) {
-        const int64_t len = load_le32(block + 8 + 4 * k);
-        if (len < 4 * lanes || len > rest) return FPCC_HOST_E_ARG;
+        const int64_t len = load_le32(block + header + 4 * k);
+        if (len < 4 * h.lanes() || len > rest) return false;
         rest -= len;
     }
-    if (rest != 0) return FPCC_HOST_E_ARG;
-    const uint8_t *payload = block + 8 + 4 * h.chunks;
+    return rest == 0;
+}
+
+// the chunks of a block whose header il_parse_header accepted.  step(j, x) decodes symbol j out of state x and advances x; false if
+// the symbol cannot be decoded.
+template <typename Step>
+int64_t il_decode_block(const uint8_t *block, int header, const IlHeader &h, Step step) {
+    const int lanes = h.lanes();
+    const uint8_t *payload = block + header + 4 * h.chunks;
     for (int64_t k = 0; k < h.chunks; ++k) {
-        const int64_t len = load_le32(block + 8 + 4 * k);
-        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, n - s0);
+        const int64_t len = load_le32(block + header + 4 * k);
+        const int64_t s0 = k * h.per_chunk, m = std::min(h.per_chunk, h.n - s0);
         uint32_t x[kIlMaxLanes];
         for (int l = 0; l < lanes; ++l) {
             x[l] = load_le32(payload + 4 * l);
@@ -1198,19 +1088,8 @@ int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const 
         const int64_t rounds = (m + lanes - 1) / lanes;
         for (int64_t r = 0; r < rounds; ++r) {
             const int active = static_cast<int>(std::min<int64_t>(lanes, m - r * lanes));
-            for (int l = 0; l < active; ++l) {
-                const int64_t j = s0 + r * lanes + l;
-                const uint16_t *row = rows + j * c;
-                const uint32_t slot = x[l] & (kProbOne - 1u);
-                int64_t s = 0;
-                for (int e = 0; e < c; ++e) s += row[e] <= slot;
-                s = std::min<int64_t>(s, c - 1);
-                uint32_t lo, hi;
-                edge_range(row, c, static_cast<uint32_t>(s), lo, hi);
-                if (hi <= lo) return FPCC_HOST_E_ARG;                 // the row does not increase at the decoded symbol
-                x[l] = (hi - lo) * (x[l] >> kProbBits) + slot - lo;
-                symbols_out[j] = static_cast<uint16_t>(s);
-            }
+            for (int l = 0; l < active; ++l)
+                if (!step(s0 + r * lanes + l, x[l])) return FPCC_HOST_E_ARG;
             for (int t = 0; t < kMaxRefill; ++t)
                 for (int l = 0; l < active; ++l)
                     if (x[l] < kLow) {
@@ -1222,6 +1101,68 @@ int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const 
         payload += len;
     }
     return FPCC_HOST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fpcc_rans_binary_il_encode(const uint8_t *bits, const uint16_t *prob1, int64_t n, int a, int b, uint8_t *out, int64_t cap) {
+    if (!out || n < 0 || cap < 0 || (n > 0 && (!bits || !prob1))) return FPCC_HOST_E_ARG;
+    return il_encode_block(0xA0, 6, n, a, b, out, cap, [&](int64_t j, uint32_t &lo, uint32_t &f) {
+        const uint32_t p = prob1[j];
+        lo = bits[j] ? kProbOne - p : 0u;
+        f = bits[j] ? p : kProbOne - p;
+        return p != 0;
+    });
+}
+
+int64_t fpcc_rans_binary_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *prob1, int64_t n, uint8_t *bits_out) {
+    if (!block || n < 0 || (n > 0 && (!prob1 || !bits_out))) return FPCC_HOST_E_ARG;
+    IlHeader h;
+    if (!il_parse_header(block, block_len, 0xA0, 6, n, h)) return FPCC_HOST_E_ARG;
+    return il_decode_block(block, 6, h, [&](int64_t j, uint32_t &x) {
+        const uint32_t p = prob1[j], split = kProbOne - p;
+        const uint32_t slot = x & (kProbOne - 1u), hi = x >> kProbBits;
+        const bool one = slot >= split;
+        x = one ? p * hi + (slot - split) : split * hi + slot;
+        bits_out[j] = static_cast<uint8_t>(one);
+        return true;
+    });
+}
+
+int64_t fpcc_rans_rows_il_encode(const uint16_t *start, const uint16_t *freq_m1, int64_t n, int c, int a, int b, uint8_t *out,
+                                 int64_t cap) {
+    if (!out || n < 0 || cap < 0 || c < 2 || c > 256 || (n > 0 && (!start || !freq_m1))) return FPCC_HOST_E_ARG;
+    const int64_t got = il_encode_block(0xB0, 8, n, a, b, out, cap, [&](int64_t j, uint32_t &lo, uint32_t &f) {
+        lo = start[j];
+        f = uint32_t(freq_m1[j]) + 1u;
+        return lo + f <= kProbOne;                                    // the range stays in the interval (f >= 1 by its representation)
+    });
+    if (got >= 8) {
+        out[6] = static_cast<uint8_t>(c);
+        out[7] = static_cast<uint8_t>(c >> 8);
+    }
+    return got;
+}
+
+int64_t fpcc_rans_rows_il_decode(const uint8_t *block, int64_t block_len, const uint16_t *rows, int64_t n, int c, uint16_t *symbols_out) {
+    if (!block || n < 0 || c < 2 || c > 256 || (n > 0 && (!rows || !symbols_out))) return FPCC_HOST_E_ARG;
+    IlHeader h;
+    if (!il_parse_header(block, block_len, 0xB0, 8, n, h) || (int(block[6]) | int(block[7]) << 8) != c) return FPCC_HOST_E_ARG;
+    return il_decode_block(block, 8, h, [&](int64_t j, uint32_t &x) {
+        const uint16_t *row = rows + j * c;
+        const uint32_t slot = x & (kProbOne - 1u);
+        int64_t s = 0;
+        for (int e = 0; e < c; ++e) s += row[e] <= slot;
+        s = std::min<int64_t>(s, c - 1);
+        uint32_t lo, hi;
+        edge_range(row, c, static_cast<uint32_t>(s), lo, hi);
+        if (hi <= lo) return false;                                   // the row does not increase at the decoded symbol
+        x = (hi - lo) * (x >> kProbBits) + slot - lo;
+        symbols_out[j] = static_cast<uint16_t>(s);
+        return true;
+    });
 }
 
 }  // extern "C"

@@ -2150,7 +2150,54 @@ def simple_dec_pop_dev(state: torch.Tensor, stream: torch.Tensor, stream_len: in
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# interleaved binary rANS blocks (one wave per chunk; INTEGRATION.md, "Interleaved occupancy blocks")
+# interleaved rANS blocks, one wave per chunk: the binary coder ("Interleaved occupancy blocks") and the simple coder,
+# one CDF row per symbol ("Interleaved row blocks"), on one container
+
+def _il_encode_dev(entry, operands, width: Optional[int], seg_edges: Sequence[int], ab: Optional[Tuple[int, int]], pairing: str):
+    """segment table, allocation and the two calls (workspace query, then the launch) of an interleaved encode entry.  operands: two
+    (tensor, dtype, name) with one element per symbol; width: the entry's row width argument, None if it has none"""
+    from .rans_coder import InterleavedBinaryCoder
+    edges = [int(e) for e in seg_edges]
+    n_seg = len(edges) - 1
+    n = operands[0][0].numel()
+    if n_seg < 1 or edges[0] < 0 or edges[-1] > n or any(b < a for a, b in zip(edges[:-1], edges[1:])) or operands[1][0].numel() != n:
+        raise ValueError('seg_edges must rise inside [0, n], ' + pairing)
+    if width is not None and not 2 <= int(width) <= 256:
+        raise ValueError('row width in 2..256 expected')
+    for a, b in [ab] if ab is not None else []:
+        if not (0 <= int(a) <= 6 and 4 <= int(b) <= 12):
+            raise ValueError('a in 0..6 and b in 4..12 expected')
+    abs_ = [ab if ab is not None else InterleavedBinaryCoder.policy(e1 - e0) for e0, e1 in zip(edges[:-1], edges[1:])]
+    dev = operands[0][0].device
+    extra = () if width is None else (int(width),)
+    table = torch.tensor(edges + [int(a) | int(b) << 8 for a, b in abs_], dtype=torch.int64, pin_memory=True)
+    offsets = torch.zeros(n_seg + 1, dtype=torch.int64)
+    need = _ok(entry(None, None, *extra, table.data_ptr(), None, n_seg, None, 0, None, None, offsets.data_ptr(), None, 0, None))
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
+    offsets = offsets.tolist()
+    out = torch.empty(max(offsets[-1], 16), dtype=torch.uint8, device=dev)
+    meta = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    table_d = table.to(dev, non_blocking=True)
+    _ok(entry(*(_dev(t, dtype, name, n == 0) for t, dtype, name in operands), *extra, table.data_ptr(), table_d.data_ptr(), n_seg,
+              out.data_ptr(), out.numel(), meta.data_ptr(), meta.data_ptr() + 8 * n_seg, None, ws.data_ptr(), int(need), _stream()))
+    return out, meta, offsets
+
+
+def _il_chunks_ok(chunks, n_seg: int):
+    if chunks.dim() != 2 or chunks.shape[1] != 6 or n_seg < 1:
+        raise ValueError('chunks must be [n_chunks, 6], n_seg >= 1')
+
+
+def _il_decode_dev(entry, blocks, chunks, operand, name: str, n: int, extra: tuple, out, n_seg: int):
+    """counts and the call of an interleaved decode entry, after _il_chunks_ok.  operand: the int16 per-symbol input; extra: the entry's
+    arguments between n and the output; out: the tensor to decode into"""
+    counts = torch.zeros(n_seg + 1, dtype=torch.int32, device=operand.device)
+    n_chunks = chunks.shape[0]
+    _ok(entry(_dev(blocks, torch.uint8, 'blocks', n_chunks == 0), blocks.numel() if blocks is not None else 0,
+              _dev(chunks, torch.int64, 'chunks', n_chunks == 0), n_chunks, _dev(operand, torch.int16, name, n_chunks == 0), n, *extra,
+              out.data_ptr(), counts.data_ptr(), int(n_seg), counts.data_ptr() + 4 * int(n_seg), _stream()))
+    return out, counts
+
 
 def rans_binary_il_encode_dev(bits: torch.Tensor, prob16: torch.Tensor, seg_edges: Sequence[int],
                               ab: Optional[Tuple[int, int]] = None):
@@ -2159,30 +2206,8 @@ def rans_binary_il_encode_dev(bits: torch.Tensor, prob16: torch.Tensor, seg_edge
     -> (out uint8 [worst case], meta int64 [n_seg + 1], offsets): block s is out[offsets[s]: offsets[s] + meta[s]], meta[n_seg] is the
     status word (non-zero: a zero probability, the blocks are void).  Nothing is synchronised: `meta` is read after the caller's own
     copy / synchronise."""
-    from .rans_coder import InterleavedBinaryCoder
-    edges = [int(e) for e in seg_edges]
-    n_seg = len(edges) - 1
-    n = bits.numel()
-    if n_seg < 1 or edges[0] < 0 or edges[-1] > n or any(b < a for a, b in zip(edges[:-1], edges[1:])) or prob16.numel() != n:
-        raise ValueError('seg_edges must rise inside [0, n], one probability per bit')
-    for a, b in [ab] if ab is not None else []:
-        if not (0 <= int(a) <= 6 and 4 <= int(b) <= 12):
-            raise ValueError('a in 0..6 and b in 4..12 expected')
-    abs_ = [ab if ab is not None else InterleavedBinaryCoder.policy(e1 - e0) for e0, e1 in zip(edges[:-1], edges[1:])]
-    dev = bits.device
-    table = torch.tensor(edges + [int(a) | int(b) << 8 for a, b in abs_], dtype=torch.int64, pin_memory=True)
-    offsets = torch.zeros(n_seg + 1, dtype=torch.int64)
-    L = lib()
-    need = _ok(L.fpcc_rans_binary_il_encode_dev(None, None, table.data_ptr(), None, n_seg, None, 0, None, None, offsets.data_ptr(), None, 0, None))
-    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
-    offsets = offsets.tolist()
-    out = torch.empty(max(offsets[-1], 16), dtype=torch.uint8, device=dev)
-    meta = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    table_d = table.to(dev, non_blocking=True)
-    _ok(L.fpcc_rans_binary_il_encode_dev(_dev(bits, torch.uint8, 'bits', n == 0), _dev(prob16, torch.int16, 'prob16', n == 0), table.data_ptr(),
-                                         table_d.data_ptr(), n_seg, out.data_ptr(), out.numel(), meta.data_ptr(), meta.data_ptr() + 8 * n_seg,
-                                         None, ws.data_ptr(), int(need), _stream()))
-    return out, meta, offsets
+    return _il_encode_dev(lib().fpcc_rans_binary_il_encode_dev, [(bits, torch.uint8, 'bits'), (prob16, torch.int16, 'prob16')], None,
+                          seg_edges, ab, 'one probability per bit')
 
 
 def rans_binary_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, prob16: torch.Tensor, n_seg: int):
@@ -2190,21 +2215,10 @@ def rans_binary_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, prob16
     builds from validated headers), prob16 int16 [n] -> (bits uint8 [n], counts int32 [n_seg + 1]: ones per segment, then the sticky
     status word, 0 = fine), all on the device; nothing is synchronised"""
     n = prob16.numel()
-    dev = prob16.device
-    if chunks.dim() != 2 or chunks.shape[1] != 6 or n_seg < 1:
-        raise ValueError('chunks must be [n_chunks, 6], n_seg >= 1')
-    bits = torch.empty(n, dtype=torch.uint8, device=dev)
-    counts = torch.zeros(n_seg + 1, dtype=torch.int32, device=dev)
-    n_chunks = chunks.shape[0]
-    _ok(lib().fpcc_rans_binary_il_decode_dev(_dev(blocks, torch.uint8, 'blocks', n_chunks == 0), blocks.numel() if blocks is not None else 0,
-                                             _dev(chunks, torch.int64, 'chunks', n_chunks == 0), n_chunks,
-                                             _dev(prob16, torch.int16, 'prob16', n_chunks == 0), n, bits.data_ptr(), counts.data_ptr(), int(n_seg),
-                                             counts.data_ptr() + 4 * int(n_seg), _stream()))
-    return bits, counts
+    _il_chunks_ok(chunks, n_seg)
+    bits = torch.empty(n, dtype=torch.uint8, device=prob16.device)
+    return _il_decode_dev(lib().fpcc_rans_binary_il_decode_dev, blocks, chunks, prob16, 'prob16', n, (), bits, n_seg)
 
-
-# ---------------------------------------------------------------------------------------------------------------
-# interleaved row blocks: the simple coder, one CDF row per symbol (one wave per chunk; INTEGRATION.md, "Interleaved row blocks")
 
 def rans_rows_il_encode_dev(start: torch.Tensor, freq_m1: torch.Tensor, width: int, seg_edges: Sequence[int],
                             ab: Optional[Tuple[int, int]] = None):
@@ -2215,33 +2229,8 @@ def rans_rows_il_encode_dev(start: torch.Tensor, freq_m1: torch.Tensor, width: i
     -> (out uint8 [worst case], meta int64 [n_seg + 1], offsets): block s is out[offsets[s]: offsets[s] + meta[s]], meta[n_seg] is the
     status word (non-zero: a range that leaves [0, 65536], the blocks are void).  Nothing is synchronised: `meta` is read after the
     caller's own copy / synchronise."""
-    from .rans_coder import InterleavedRowCoder
-    edges = [int(e) for e in seg_edges]
-    n_seg = len(edges) - 1
-    n = start.numel()
-    if n_seg < 1 or edges[0] < 0 or edges[-1] > n or any(b < a for a, b in zip(edges[:-1], edges[1:])) or freq_m1.numel() != n:
-        raise ValueError('seg_edges must rise inside [0, n], one (start, freq - 1) pair per symbol')
-    if not 2 <= int(width) <= 256:
-        raise ValueError('row width in 2..256 expected')
-    for a, b in [ab] if ab is not None else []:
-        if not (0 <= int(a) <= 6 and 4 <= int(b) <= 12):
-            raise ValueError('a in 0..6 and b in 4..12 expected')
-    abs_ = [ab if ab is not None else InterleavedRowCoder.policy(e1 - e0) for e0, e1 in zip(edges[:-1], edges[1:])]
-    dev = start.device
-    table = torch.tensor(edges + [int(a) | int(b) << 8 for a, b in abs_], dtype=torch.int64, pin_memory=True)
-    offsets = torch.zeros(n_seg + 1, dtype=torch.int64)
-    L = lib()
-    need = _ok(L.fpcc_rans_rows_il_encode_dev(None, None, int(width), table.data_ptr(), None, n_seg, None, 0, None, None, offsets.data_ptr(),
-                                              None, 0, None))
-    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=dev)
-    offsets = offsets.tolist()
-    out = torch.empty(max(offsets[-1], 16), dtype=torch.uint8, device=dev)
-    meta = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
-    table_d = table.to(dev, non_blocking=True)
-    _ok(L.fpcc_rans_rows_il_encode_dev(_dev(start, torch.int16, 'start', n == 0), _dev(freq_m1, torch.int16, 'freq_m1', n == 0), int(width),
-                                       table.data_ptr(), table_d.data_ptr(), n_seg, out.data_ptr(), out.numel(), meta.data_ptr(),
-                                       meta.data_ptr() + 8 * n_seg, None, ws.data_ptr(), int(need), _stream()))
-    return out, meta, offsets
+    return _il_encode_dev(lib().fpcc_rans_rows_il_encode_dev, [(start, torch.int16, 'start'), (freq_m1, torch.int16, 'freq_m1')], width,
+                          seg_edges, ab, 'one (start, freq - 1) pair per symbol')
 
 
 def rans_rows_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, rows: torch.Tensor, n_seg: int,
@@ -2253,17 +2242,9 @@ def rans_rows_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, rows: to
     if rows.dim() != 2 or not 2 <= rows.shape[1] <= 256:
         raise ValueError('rows must be [n, c] with c in 2..256')
     n, c = rows.shape
-    dev = rows.device
-    if chunks.dim() != 2 or chunks.shape[1] != 6 or n_seg < 1:
-        raise ValueError('chunks must be [n_chunks, 6], n_seg >= 1')
-    sym = torch.empty(n, dtype=torch.int16, device=dev) if symbols_out is None else symbols_out
+    _il_chunks_ok(chunks, n_seg)
+    sym = torch.empty(n, dtype=torch.int16, device=rows.device) if symbols_out is None else symbols_out
     if sym.numel() != n:
         raise ValueError('symbols_out must hold one symbol per row')
     _dev(sym, torch.int16, 'symbols_out', n == 0)
-    counts = torch.zeros(n_seg + 1, dtype=torch.int32, device=dev)
-    n_chunks = chunks.shape[0]
-    _ok(lib().fpcc_rans_rows_il_decode_dev(_dev(blocks, torch.uint8, 'blocks', n_chunks == 0), blocks.numel() if blocks is not None else 0,
-                                           _dev(chunks, torch.int64, 'chunks', n_chunks == 0), n_chunks,
-                                           _dev(rows, torch.int16, 'rows', n_chunks == 0), n, int(c), sym.data_ptr(), counts.data_ptr(),
-                                           int(n_seg), counts.data_ptr() + 4 * int(n_seg), _stream()))
-    return sym, counts
+    return _il_decode_dev(lib().fpcc_rans_rows_il_decode_dev, blocks, chunks, rows, 'rows', n, (int(c),), sym, n_seg)

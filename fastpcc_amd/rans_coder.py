@@ -151,10 +151,12 @@ class BinaryRansCoder:
         return 0
 
 
-class InterleavedBinaryCoder:
-    """The binary coder with 2^a interleaved states: one block per call (INTEGRATION.md, "Interleaved occupancy blocks").  The host
-    pair of libfpcc_host; the device pair is hipops.rans_binary_il_encode_dev / rans_binary_il_decode_dev -- same bytes."""
-    TAG = 0xA0
+class _InterleavedBlocks:
+    """The container the two interleaved formats share: 2^a states per chunk, chunks of 2^(a + b) symbols, a block = header | chunk
+    lengths | chunks.  A subclass names its tag byte, header size and messages, and checks what its header holds past byte 6."""
+    TAG = HEADER = None
+    _NAME = None              # prefix of every message
+    _COUNTED = None           # what the level has one symbol for, in the message about n
 
     @staticmethod
     def policy(n: int) -> Tuple[int, int]:
@@ -170,48 +172,70 @@ class InterleavedBinaryCoder:
 
     @classmethod
     def worst_case_bytes(cls, n: int, a: int, b: int) -> int:
-        """header + lengths + per chunk the initial states and two bytes per symbol"""
+        """header + lengths + per chunk the initial states and two bytes per symbol (a symbol emits at most two: freq >= 1)"""
         k = cls.n_chunks(n, a, b)
-        return 6 + 4 * k + 4 * (1 << a) * k + 2 * n
+        return cls.HEADER + 4 * k + 4 * (1 << a) * k + 2 * n
 
     @classmethod
-    def parse_header(cls, block, n: int) -> Tuple[int, int, List[int]]:
-        """(a, b, chunk payload lengths) of a block that codes n symbols; ValueError for anything a decoder must not be started on"""
+    def _check_width(cls, block, c):
+        """the header's bytes past 6 against what the caller expects; the 6-byte header has none"""
+
+    @classmethod
+    def _parse_header(cls, block, n: int, c=None) -> Tuple[int, int, List[int]]:
         block = memoryview(block)
-        if len(block) < 6:
-            raise ValueError('interleaved block: shorter than its header')
+        if len(block) < cls.HEADER:
+            raise ValueError(f'{cls._NAME}: shorter than its header')
         if block[0] & 0xF8 != cls.TAG:
-            raise ValueError('interleaved block: wrong tag byte')
+            raise ValueError(f'{cls._NAME}: wrong tag byte')
         a, b = block[0] & 7, block[1]
         if a > 6 or not 4 <= b <= 12:
-            raise ValueError('interleaved block: lanes = 2^a with a in 0..6 and symbols per lane = 2^b with b in 4..12')
+            raise ValueError(f'{cls._NAME}: lanes = 2^a with a in 0..6 and symbols per lane = 2^b with b in 4..12')
         if int.from_bytes(block[2:6], 'little') != n:
-            raise ValueError('interleaved block: codes another number of symbols than the level has candidates')
+            raise ValueError(f'{cls._NAME}: codes another number of symbols than the level has {cls._COUNTED}')
+        cls._check_width(block, c)
         k = cls.n_chunks(n, a, b)
-        if len(block) < 6 + 4 * k:
-            raise ValueError('interleaved block: shorter than its table of chunk lengths')
-        lens = np.frombuffer(block[6:6 + 4 * k], dtype='<u4').astype(np.int64).tolist()
+        if len(block) < cls.HEADER + 4 * k:
+            raise ValueError(f'{cls._NAME}: shorter than its table of chunk lengths')
+        lens = np.frombuffer(block[cls.HEADER:cls.HEADER + 4 * k], dtype='<u4').astype(np.int64).tolist()
         if any(v < 4 << a for v in lens):
-            raise ValueError('interleaved block: a chunk shorter than its initial states')
-        if sum(lens) != len(block) - 6 - 4 * k:
-            raise ValueError('interleaved block: chunk lengths do not sum to the payload')
+            raise ValueError(f'{cls._NAME}: a chunk shorter than its initial states')
+        if sum(lens) != len(block) - cls.HEADER - 4 * k:
+            raise ValueError(f'{cls._NAME}: chunk lengths do not sum to the payload')
         return a, b, lens
 
     @classmethod
-    def chunk_table(cls, block, n: int, block_at: int, sym0: int, seg: int) -> np.ndarray:
-        """int64 [K, 6] descriptors of a VALIDATED block for fpcc_rans_binary_il_decode_dev: the block lies at byte `block_at` of the
-        device buffer and codes symbols [sym0, sym0 + n) of segment `seg`"""
-        a, b, lens = cls.parse_header(block, n)
+    def _chunk_table(cls, block, n: int, c, block_at: int, sym0: int, seg: int) -> np.ndarray:
+        a, b, lens = cls._parse_header(block, n, c)
         k = len(lens)
         out = np.empty((k, 6), dtype=np.int64)
         lens = np.asarray(lens, dtype=np.int64)
-        out[:, 0] = block_at + 6 + 4 * k + np.cumsum(lens) - lens
+        out[:, 0] = block_at + cls.HEADER + 4 * k + np.cumsum(lens) - lens
         out[:, 1] = lens
         out[:, 2] = sym0 + (np.arange(k, dtype=np.int64) << (a + b))
         out[:, 3] = np.minimum(1 << (a + b), n - (np.arange(k, dtype=np.int64) << (a + b)))
         out[:, 4] = seg
         out[:, 5] = a
         return out
+
+
+class InterleavedBinaryCoder(_InterleavedBlocks):
+    """The binary coder with 2^a interleaved states: one block per call (INTEGRATION.md, "Interleaved occupancy blocks").  The host
+    pair of libfpcc_host; the device pair is hipops.rans_binary_il_encode_dev / rans_binary_il_decode_dev -- same bytes."""
+    TAG = 0xA0
+    HEADER = 6
+    _NAME = 'interleaved block'
+    _COUNTED = 'candidates'
+
+    @classmethod
+    def parse_header(cls, block, n: int) -> Tuple[int, int, List[int]]:
+        """(a, b, chunk payload lengths) of a block that codes n symbols; ValueError for anything a decoder must not be started on"""
+        return cls._parse_header(block, n)
+
+    @classmethod
+    def chunk_table(cls, block, n: int, block_at: int, sym0: int, seg: int) -> np.ndarray:
+        """int64 [K, 6] descriptors of a VALIDATED block for fpcc_rans_binary_il_decode_dev: the block lies at byte `block_at` of the
+        device buffer and codes symbols [sym0, sym0 + n) of segment `seg`"""
+        return cls._chunk_table(block, n, None, block_at, sym0, seg)
 
     def encode(self, symbol_array: np.ndarray, prob_array: np.ndarray, a: Optional[int] = None, b: Optional[int] = None) -> bytes:
         bits = np.ascontiguousarray(np.asarray(symbol_array).reshape(-1) != 0).view(np.uint8)
@@ -242,62 +266,31 @@ class InterleavedBinaryCoder:
         return out
 
 
-class InterleavedRowCoder:
+class InterleavedRowCoder(_InterleavedBlocks):
     """The simple coder (one CDF row per symbol) with 2^a interleaved states: one block per call ("Interleaved row
     blocks").  The host pair of libfpcc_host; the device pair is hipops.rans_rows_il_encode_dev / rans_rows_il_decode_dev -- same
     bytes.  Chunk geometry and default policy are InterleavedBinaryCoder's."""
     TAG = 0xB0
     HEADER = 8
-    policy = staticmethod(InterleavedBinaryCoder.policy)
-    n_chunks = staticmethod(InterleavedBinaryCoder.n_chunks)
+    _NAME = 'interleaved row block'
+    _COUNTED = 'voxels'
 
     @classmethod
-    def worst_case_bytes(cls, n: int, a: int, b: int) -> int:
-        """header + lengths + per chunk the initial states and two bytes per symbol (a symbol emits at most two: freq >= 1)"""
-        k = cls.n_chunks(n, a, b)
-        return cls.HEADER + 4 * k + 4 * (1 << a) * k + 2 * n
+    def _check_width(cls, block, c):
+        if not 2 <= c <= 256 or int.from_bytes(block[6:8], 'little') != c:
+            raise ValueError('interleaved row block: coded under rows of another width (2..256)')
 
     @classmethod
     def parse_header(cls, block, n: int, c: int) -> Tuple[int, int, List[int]]:
         """(a, b, chunk payload lengths) of a block that codes n symbols under rows of width c; ValueError for anything a decoder must
         not be started on"""
-        block = memoryview(block)
-        if len(block) < cls.HEADER:
-            raise ValueError('interleaved row block: shorter than its header')
-        if block[0] & 0xF8 != cls.TAG:
-            raise ValueError('interleaved row block: wrong tag byte')
-        a, b = block[0] & 7, block[1]
-        if a > 6 or not 4 <= b <= 12:
-            raise ValueError('interleaved row block: lanes = 2^a with a in 0..6 and symbols per lane = 2^b with b in 4..12')
-        if int.from_bytes(block[2:6], 'little') != n:
-            raise ValueError('interleaved row block: codes another number of symbols than the level has voxels')
-        if not 2 <= c <= 256 or int.from_bytes(block[6:8], 'little') != c:
-            raise ValueError('interleaved row block: coded under rows of another width (2..256)')
-        k = cls.n_chunks(n, a, b)
-        if len(block) < cls.HEADER + 4 * k:
-            raise ValueError('interleaved row block: shorter than its table of chunk lengths')
-        lens = np.frombuffer(block[cls.HEADER:cls.HEADER + 4 * k], dtype='<u4').astype(np.int64).tolist()
-        if any(v < 4 << a for v in lens):
-            raise ValueError('interleaved row block: a chunk shorter than its initial states')
-        if sum(lens) != len(block) - cls.HEADER - 4 * k:
-            raise ValueError('interleaved row block: chunk lengths do not sum to the payload')
-        return a, b, lens
+        return cls._parse_header(block, n, c)
 
     @classmethod
     def chunk_table(cls, block, n: int, c: int, block_at: int, sym0: int, seg: int) -> np.ndarray:
         """int64 [K, 6] descriptors of a VALIDATED block for fpcc_rans_rows_il_decode_dev: the block lies at byte `block_at` of the
         device buffer and codes symbols [sym0, sym0 + n) of segment `seg`"""
-        a, b, lens = cls.parse_header(block, n, c)
-        k = len(lens)
-        out = np.empty((k, 6), dtype=np.int64)
-        lens = np.asarray(lens, dtype=np.int64)
-        out[:, 0] = block_at + cls.HEADER + 4 * k + np.cumsum(lens) - lens
-        out[:, 1] = lens
-        out[:, 2] = sym0 + (np.arange(k, dtype=np.int64) << (a + b))
-        out[:, 3] = np.minimum(1 << (a + b), n - (np.arange(k, dtype=np.int64) << (a + b)))
-        out[:, 4] = seg
-        out[:, 5] = a
-        return out
+        return cls._chunk_table(block, n, c, block_at, sym0, seg)
 
     @staticmethod
     def ranges_of(rows: np.ndarray, symbols: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
