@@ -1698,6 +1698,12 @@ extern "C" int fpcc_conv_f32_pk(const float *x1, int c1, int ld1, const float *x
     const int ch = plan.chunk;
     if (row_order && !plan.matrix)
         return fail_arg("conv_f32: row_order is a feature of the matrix path (fpcc_conv_f32_order() != 0 or fpcc_conv_f32_natural_matrix())");
+    // Beside a row order a row-major table is indexed by TILE POSITION (fpcc_hip.h), and the kernels read it that way only where they
+    // fetch its rows as 16-byte pieces (table_is_row_major): any other nbr_ks == 1 table they would read by output row without a word.
+    // Decided here, once, for every kernel.  A map of one row has one position, which is its row: [K][1] and [1][K] are the same table.
+    if (row_order && nbr && nbr_ks == 1 && n_out > 1 && !((nbr_os & 3) == 0 && nbr_os >= ((n_offsets + 3) & ~3) && aligned16(nbr)))
+        return fail_arg("conv_f32: beside a row_order a row-major table (nbr_ks == 1) is read by tile position and needs nbr_os a multiple of 4, "
+                        "nbr_os >= n_offsets rounded up to a multiple of 4, and a 16-byte aligned pointer");
     // The matrix kernel needs what the VALU kernel never asked of these shapes: 16-byte aligned rows, and packed weights or a workspace
     // to pack into.  A call without them is served as it always was, by k_conv_valu -- the same chain, the same bits.
     const bool nat_operands = aligned16(x1) && ld1 % 4 == 0 && (c2 == 0 || (aligned16(x2) && ld2 % 4 == 0)) &&

@@ -709,7 +709,11 @@ def conv_f32(x1: torch.Tensor, w: torch.Tensor, c_out: int, n_out: int, *, x2: O
              row_order: Optional[torch.Tensor] = None, pack: bool = False) -> torch.Tensor:
     """out[dst(o,g)] = act(sum_k X[nbr[k*nbr_ks + o*nbr_os]] @ w[g][k] + bias); see include/fpcc_hip.h.
     pack: True = keep a packed copy of `w` (packed_weights) and run the shapes that have one on the wave-autonomous / persistent
-    per-point kernels -- for weights that stay put between calls (inference); 'fresh' = pack for this call only (training)."""
+    per-point kernels -- for weights that stay put between calls (inference); 'fresh' = pack for this call only (training).
+    row_order: beside it an offset-major table (nbr_ks != 1) is indexed by output row, a row-major one (nbr_ks == 1) by tile position
+    (gather_table_rows).  Such a table (n_out > 1) must have nbr_os a multiple of 4, nbr_os >= n_offsets rounded up to a multiple of 4
+    and a 16-byte aligned pointer -- transpose_table / gather_table_rows output and child_row [m, 8] qualify; any other nbr_ks == 1
+    table beside a row order raises FpccError.  Without a row order every (nbr_ks, nbr_os) is taken."""
     p1, c1, ld1 = _rows2d(x1, 'x1')
     if x2 is not None:
         p2, c2, ld2 = _rows2d(x2, 'x2')

@@ -385,7 +385,12 @@ int fpcc_pointwise_head_f32(const float *x, int c0, int ldx, const float *w1, co
  * Table layout beside a row order: an offset-major table (nbr_ks != 1) is indexed by OUTPUT ROW as always; a ROW-MAJOR table
  * (nbr_ks == 1, fpcc_transpose_table_i32) is indexed by TILE POSITION -- its row p holds the neighbours of output row row_order[p]
  * (gather the table's rows by row_order once per coordinate map) -- so that the entries a block of positions needs are consecutive
- * in memory and no load of a kernel's prologue depends on another. */
+ * in memory and no load of a kernel's prologue depends on another.  Such a table is fetched as 16-byte pieces, so beside a row
+ * order (and n_out > 1) a table with nbr_ks == 1 must have nbr_os a multiple of 4, nbr_os >= n_offsets rounded up to a multiple
+ * of 4, and a 16-byte aligned pointer -- what fpcc_transpose_table_i32 / fpcc_gather_table_rows_i32 and child_row [m][8] give.
+ * fpcc_conv_f32 / fpcc_conv_f32_pk refuse any other nbr_ks == 1 table beside a row order with FPCC_E_ARG (a [n][27] table, a
+ * pointer 4 bytes into a buffer): the kernels would read it by output row.  Without a row order position and row are the same
+ * and every (nbr_ks, nbr_os) is taken, aligned or not. */
 int fpcc_conv_row_keys(const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os, int64_t n, int window_log2,
                        int64_t *keys_out, uint32_t *masks_out, void *stream);
 /* masks_out (may be NULL): per row, bit k set iff the row has kernel offset k. */
