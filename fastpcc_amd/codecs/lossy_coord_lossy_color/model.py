@@ -18,6 +18,8 @@ from .layers import Decoder, DecoderGeoLossl, Encoder, EncoderGeoLossl, HyperDec
     ResidualGeoLossl
 from .model_config import ModelConfig
 
+BF16_MARK = 0x80       # first header byte (numerics_version_in_header): set when the stream was written with inference_dtype = 'bfloat16'
+
 
 class PCC(nn.Module):
 
@@ -45,6 +47,32 @@ class PCC(nn.Module):
             hyper_decoder_coord=HyperDecoderGenUpsample(ch[1:], cfg.geo_lossl_if_sample, region, act),
             hyper_decoder_fea=HyperDecoderUpsample(ch[1:], ch[:-1], cfg.geo_lossl_if_sample, region, act))
         self.em_lossless_based.occupancy_format = cfg.occupancy_stream_format
+        if self._inference_dtype == 'bfloat16':
+            ME.mark_bf16_producers(self, hipops.FPCC_BF16_PROFILE_COLOR)
+
+    # the two keys of model_config.InferenceModelConfig; a plain ModelConfig has neither and means fp32, no version byte
+    @property
+    def _inference_dtype(self) -> str:
+        return getattr(self.cfg, 'inference_dtype', '')
+
+    @property
+    def _version_in_header(self) -> bool:
+        return bool(getattr(self.cfg, 'numerics_version_in_header', False))
+
+    def set_inference_dtype(self, name: str) -> None:
+        """switch a built model between '' (fp32) and 'bfloat16' inference: what the `inference_dtype` key does at construction, for a
+        caller that only holds the model.  Validated by the config class ('float16' is refused by name)."""
+        self.cfg = self.cfg.with_inference(inference_dtype=name)
+        if name == 'bfloat16':
+            ME.mark_bf16_producers(self, hipops.FPCC_BF16_PROFILE_COLOR)
+
+    def _inference_context(self):
+        """what the six coding calls run the networks in: cfg.inference_dtype = 'bfloat16' opens ME.conv_inference_dtype under profile 2
+        (hipops.FPCC_BF16_PROFILE_COLOR: lossy_coord_v2's set plus the narrow 3x3x3 layers), '' the fp32 path explicitly (a default
+        model called from inside somebody's bf16 context still writes fp32 streams)"""
+        if self._inference_dtype == 'bfloat16':
+            return ME.conv_inference_dtype(torch.bfloat16, profile=hipops.FPCC_BF16_PROFILE_COLOR)
+        return ME.conv_inference_dtype(None)
 
     def forward(self, pc_data: PCData):
         if self.training:
@@ -107,13 +135,20 @@ class PCC(nn.Module):
         if not batched_coord.is_cuda:
             raise RuntimeError('compress() runs on the GPU; move the inputs there first')
         coord_offset = batched_coord.amin(0)[1:]
-        sparse_pc = self.get_sparse_pc((batched_coord - F.pad(coord_offset, (1, 0))).contiguous(), batched_color)
-        feature, points_num_list = self.encoder(sparse_pc)
-        em_bytes = self.em_lossless_based.compress(feature, 1)
+        with self._inference_context():
+            sparse_pc = self.get_sparse_pc((batched_coord - F.pad(coord_offset, (1, 0))).contiguous(), batched_color)
+            feature, points_num_list = self.encoder(sparse_pc)
+            em_bytes = self.em_lossless_based.compress(feature, 1)
         return self._header(coord_offset.tolist(), None if points_num_list is None else [counts[0] for counts in points_num_list]) + em_bytes
 
     def _header(self, coord_offset: List[int], counts: Optional[List[int]]) -> bytes:
-        head = b''.join(int(v).to_bytes(2, 'little', signed=False) for v in coord_offset)
+        head = b''
+        if self._version_in_header:
+            head = bytes([hipops.numerics_version()])
+            if self._inference_dtype == 'bfloat16':
+                # the marker of a bf16 stream: the top bit of the numerics byte, then the version of the eligible-layer set
+                head = bytes([hipops.numerics_version() | BF16_MARK, hipops.FPCC_BF16_PROFILE_COLOR])
+        head += b''.join(int(v).to_bytes(2, 'little', signed=False) for v in coord_offset)
         if self.cfg.adaptive_pruning:
             head += b''.join(int(n).to_bytes(3, 'little', signed=False) for n in counts)
         return head
@@ -131,9 +166,10 @@ class PCC(nn.Module):
         offsets = torch.stack([c.amin(0) for c in clouds])
         shift = offsets.clone()
         shift[:, 0] = -torch.arange(B, device=shift.device, dtype=shift.dtype)
-        sparse_pc = self.get_sparse_pc(torch.cat([c - shift[b] for b, c in enumerate(clouds)]), torch.cat(list(colors)), clouds=B)
-        feature, points_num_list = self.encoder(sparse_pc)
-        em_bytes = self.em_lossless_based.compress_clouds(feature, B)
+        with self._inference_context():
+            sparse_pc = self.get_sparse_pc(torch.cat([c - shift[b] for b, c in enumerate(clouds)]), torch.cat(list(colors)), clouds=B)
+            feature, points_num_list = self.encoder(sparse_pc)
+            em_bytes = self.em_lossless_based.compress_clouds(feature, B)
         offsets = offsets[:, 1:].tolist()
         return [self._header(offsets[b], None if points_num_list is None else [counts[b] for counts in points_num_list]) + em_bytes[b]
                 for b in range(B)]
@@ -150,9 +186,10 @@ class PCC(nn.Module):
         points_num_list = None
         if self.cfg.adaptive_pruning:
             points_num_list = [[parsed[b][1][s][0] for b in range(B)] for s in range(len(parsed[0][1]))]
-        cm = self.set_global_cm(B)
-        fea_recon = self.em_lossless_based.decompress_clouds([p[2] for p in parsed], cm)
-        out = self.decoder(fea_recon, points_num_list)
+        with self._inference_context():
+            cm = self.set_global_cm(B)
+            fea_recon = self.em_lossless_based.decompress_clouds([p[2] for p in parsed], cm)
+            out = self.decoder(fea_recon, points_num_list)
         edges = cm.batch_offsets(cm._map(out.coordinate_map_key))
         xyz, rgb = out.C[:, 1:], out.F.round_()
         return [(xyz[a:b] + offset[c], rgb[a:b]) for c, (a, b) in enumerate(zip(edges[:-1], edges[1:]))]
@@ -174,12 +211,28 @@ class PCC(nn.Module):
     def compress_partitions(self, batched_coord: List[torch.Tensor], batched_color: List[torch.Tensor]) -> bytes:
         coords, colors = list(batched_coord[1:]), list(batched_color[1:])      # element 0 is the unpartitioned cloud
         coded: List[bytes] = []
-        for g in self._groups([c.shape[0] for c in coords]):
-            coded.extend(self.compress_many([coords[i] for i in g], [colors[i] for i in g]))
+        with self._inference_context():
+            for g in self._groups([c.shape[0] for c in coords]):
+                coded.extend(self.compress_many([coords[i] for i in g], [colors[i] for i in g]))
         return b''.join(len(s).to_bytes(3, 'little', signed=False) + s for s in coded)
 
     def _parse_header(self, compressed_bytes: bytes):
         with io.BytesIO(compressed_bytes) as bs:
+            if self._version_in_header:
+                written_by = bs.read(1)[0]
+                bf16 = self._inference_dtype == 'bfloat16'
+                if bool(written_by & BF16_MARK) != bf16:
+                    raise ValueError('stream written with bfloat16 inference, this model decodes fp32 streams' if not bf16 else
+                                     'stream written with fp32 inference, this model (inference_dtype = bfloat16) decodes bfloat16 streams')
+                written_by &= BF16_MARK - 1
+                if bf16:
+                    profile = bs.read(1)[0]
+                    if profile != hipops.FPCC_BF16_PROFILE_COLOR:
+                        raise ValueError(f'stream written with bfloat16 profile version {profile}, this build decodes version '
+                                         f'{hipops.FPCC_BF16_PROFILE_COLOR} (the set of bf16 layers is part of the format)')
+                if written_by != hipops.numerics_version():
+                    raise ValueError(f'stream written with numerics version {written_by}, this build decodes version '
+                                     f'{hipops.numerics_version()} (the fp32 summation orders are part of the format)')
             coord_offset = [int.from_bytes(bs.read(2), 'little', signed=False) for _ in range(3)]
             points_num_list = None
             if self.cfg.adaptive_pruning:
@@ -193,8 +246,9 @@ class PCC(nn.Module):
         dev = next(self.parameters()).device
         coord_offset, points_num_list, em_bytes = self._parse_header(compressed_bytes)
         offset = torch.tensor(coord_offset, dtype=torch.int32, device=dev)      # before anything is queued (pageable H2D waits)
-        fea_recon = self.em_lossless_based.decompress(em_bytes, self.set_global_cm())
-        out = self.decoder(fea_recon, points_num_list)
+        with self._inference_context():
+            fea_recon = self.em_lossless_based.decompress(em_bytes, self.set_global_cm())
+            out = self.decoder(fea_recon, points_num_list)
         coord = out.C[:, 1:] + offset
         return coord, out.F.round_()
 
@@ -207,10 +261,11 @@ class PCC(nn.Module):
         # a partition's size before it is decoded: the pruning target of the finest stage in its header
         sizes = [self._parse_header(s)[1][0][0] if self.cfg.adaptive_pruning else len(s) for s in streams]
         coords, colors = [], []
-        for g in self._groups(sizes):
-            for c, f in self.decompress_many([streams[i] for i in g]):
-                coords.append(c)
-                colors.append(f)
+        with self._inference_context():
+            for g in self._groups(sizes):
+                for c, f in self.decompress_many([streams[i] for i in g]):
+                    coords.append(c)
+                    colors.append(f)
         return torch.cat(coords, 0), torch.cat(colors, 0)
 
     def test_forward(self, pc_data: PCData) -> dict:

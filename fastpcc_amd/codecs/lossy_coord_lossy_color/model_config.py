@@ -56,7 +56,36 @@ class ModelConfig:
         merged = {}
         for section in _load_with_includes(path):
             merged.update(section.get('model') or {})
+        if cls is ModelConfig and merged.keys() & {'inference_dtype', 'numerics_version_in_header'}:
+            cls = InferenceModelConfig                   # the keys of the inference modes live in the extended class
         return cls(**merged)
+
+    def with_inference(self, **keys) -> 'InferenceModelConfig':
+        """this configuration as an InferenceModelConfig, with `keys` (inference_dtype, numerics_version_in_header, or any other field)
+        replaced"""
+        return InferenceModelConfig(**{**{f.name: getattr(self, f.name) for f in fields(self)}, **keys})
+
+
+@dataclass
+class InferenceModelConfig(ModelConfig):
+    """ModelConfig plus the two keys of the inference modes, which are no keys of the reference's config (ModelConfig itself keeps
+    exactly the fields it had, and a model built from one behaves and writes as before):"""
+    # True prepends one byte, the numerics version of the build that wrote the stream (lossy_coord_v2's key of the same name).
+    # Default False = the reference's byte layout exactly.
+    numerics_version_in_header: bool = False
+    # '' = fp32 inference, the reference's bytes; 'bfloat16' = the convolution layers of
+    # hipops.bf16_profile_eligible(..., profile=hipops.FPCC_BF16_PROFILE_COLOR) run with bf16 operands on the bf16 matrix pipe in
+    # compress and decompress alike.  Such a stream decodes only with a model in the same mode; with numerics_version_in_header it
+    # says so in its first two bytes.
+    inference_dtype: str = ''
+
+    def __post_init__(self):
+        if self.inference_dtype == 'float16':
+            raise ValueError("inference_dtype 'float16' is not offered: use 'bfloat16' (the fp32 range, and the rate of the same matrix "
+                             "instructions on gfx950)")
+        if self.inference_dtype not in ('', 'bfloat16'):
+            raise ValueError("inference_dtype must be '' (fp32) or 'bfloat16'")
+        super().__post_init__()
 
 
 def baseline_r1() -> ModelConfig:

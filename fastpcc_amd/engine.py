@@ -93,27 +93,44 @@ class conv_inference_dtype:
     sends every layer of hipops.bf16_inference_eligible to fpcc_conv_bf16_fused -- bf16 operands on the bf16 matrix pipe, fp32
     accumulation, fp32 results; every other layer, and everything outside the context, keeps its fp32 evaluation and its bits.  Which
     layers are sent is a function of their kind and channel counts alone (part of the stream format of a codec run in this mode).
-    Separate from conv_autocast (training), which inference ignores.  None / torch.float32: the fp32 path.  Re-entrant."""
+    Separate from conv_autocast (training), which inference ignores.  None / torch.float32: the fp32 path.  Re-entrant.
+    profile: which set of layers is sent -- hipops.FPCC_BF16_PROFILE_VERSION (1, the default: lossy_coord_v2's frozen set) or
+    hipops.FPCC_BF16_PROFILE_COLOR (2: that set plus the narrow 3x3x3 layers, which go to fpcc_conv_bf16_narrow)."""
 
-    def __init__(self, dtype=torch.bfloat16):
+    def __init__(self, dtype=torch.bfloat16, profile: int = 1):
         if dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError(f'conv_inference_dtype takes torch.bfloat16 or torch.float32, not {dtype} '
                              '(float16 is not offered: gfx950 has no advantage for it over bfloat16 and its range is too small)')
+        if profile not in (ops.FPCC_BF16_PROFILE_VERSION, ops.FPCC_BF16_PROFILE_COLOR):
+            raise ValueError(f'unknown bfloat16 inference profile {profile!r}')
         self.dtype = None if dtype == torch.float32 else dtype
+        self.profile = int(profile)
 
     def __enter__(self):
-        self._prev = getattr(_tls, 'infer_dtype', None)
+        self._prev = (getattr(_tls, 'infer_dtype', None), getattr(_tls, 'infer_profile', 1))
         _tls.infer_dtype = self.dtype
+        _tls.infer_profile = self.profile
         return self
 
     def __exit__(self, *exc):
-        _tls.infer_dtype = self._prev
+        _tls.infer_dtype, _tls.infer_profile = self._prev
         return False
 
 
 def inference_dtype():
     """torch.bfloat16 inside conv_inference_dtype(torch.bfloat16) on this thread, else None"""
     return getattr(_tls, 'infer_dtype', None)
+
+
+def inference_profile() -> int:
+    """the bf16 profile of the innermost conv_inference_dtype context of this thread (1 outside any); read with inference_dtype()"""
+    return getattr(_tls, 'infer_profile', 1)
+
+
+def _narrow_bf16(kind: str, c1: int, c2: int, c_out: int) -> bool:
+    """whether the layer runs on fpcc_conv_bf16_narrow here: bf16 context, profile 2, a layer of the narrow set"""
+    return inference_dtype() is torch.bfloat16 and inference_profile() == ops.FPCC_BF16_PROFILE_COLOR and \
+        ops.bf16_narrow_eligible(kind, c1, c2, c_out)
 
 
 def _as_stride(s) -> Tuple[int, int, int]:
@@ -627,6 +644,7 @@ class SparseTensor:
         # made on).  A cache of part.bfloat16(), never a definition: written by a producing bf16 layer that was asked to, else cast once
         # on first use (bf16_parts)
         self._bf16: Optional[list] = None
+        self._bf16_pad: Optional[list] = None          # the same for the parts zero-padded to whole 16-channel steps (bf16_parts(pad16=True))
         n_rows = coordinate_manager._map(coordinate_map_key).n
         for f in self._parts:
             if f.shape[0] != n_rows:
@@ -638,17 +656,22 @@ class SparseTensor:
         if len(self._parts) > 1:
             self._parts = (torch.cat(self._parts, dim=1),)
             self._bf16 = None
+            self._bf16_pad = None
         return self._parts[0]
 
     @property
     def parts(self) -> Tuple[torch.Tensor, ...]:
         return self._parts
 
-    def bf16_parts(self) -> Tuple[torch.Tensor, ...]:
+    def bf16_parts(self, pad16: bool = False) -> Tuple[torch.Tensor, ...]:
         """the parts as bfloat16 rows (round to nearest even): the companion a producing layer wrote, else ONE fpcc_cast_f32_bf16 per part,
         kept -- a tensor read by several bf16 layers (`lower` of a pyramid level: both hyper decoders) is cast once.  A companion made on
         another stream than the caller's (the occupancy predictors may run on a side stream) is waited for.  The cache assumes what the
-        engine's own layers guarantee: the features of a tensor that a convolution has read are not written in place afterwards."""
+        engine's own layers guarantee: the features of a tensor that a convolution has read are not written in place afterwards.
+        pad16: every part zero-padded to a multiple of 16 channels (fpcc_cast_pad_f32_bf16, any width and pitch), cached per part beside
+        the unpadded form; a part of whole 16-channel steps IS its unpadded form, so a producer's companion serves both."""
+        if pad16:
+            return self._bf16_parts_pad16()
         if self._bf16 is None:
             self._bf16 = [None] * len(self._parts)
         cur = ops._stream()
@@ -659,6 +682,26 @@ class SparseTensor:
                 if p.stride(1) != 1 or p.stride(0) % 4 or p.data_ptr() % 16:
                     p = p.contiguous()                   # (the cast reads whole 16-byte pieces)
                 ent = self._bf16[i] = (ops.cast_bf16(p), cur)
+            elif ent[1] != cur:
+                here = torch.cuda.current_stream()
+                here.wait_stream(torch.cuda.ExternalStream(ent[1]) if ent[1] else torch.cuda.default_stream())
+                ent[0].record_stream(here)
+            out.append(ent[0])
+        return tuple(out)
+
+    def _bf16_parts_pad16(self) -> Tuple[torch.Tensor, ...]:
+        if self._bf16 is None:
+            self._bf16 = [None] * len(self._parts)
+        if self._bf16_pad is None:
+            self._bf16_pad = [None] * len(self._parts)
+        cur = ops._stream()
+        out = []
+        for i, p in enumerate(self._parts):
+            whole = p.shape[1] % 16 == 0
+            cache = self._bf16 if whole else self._bf16_pad
+            ent = cache[i]
+            if ent is None:
+                ent = cache[i] = (ops.cast_bf16(p if p.stride(1) == 1 or p.shape[1] == 1 else p.contiguous(), pad16=True), cur)
             elif ent[1] != cur:
                 here = torch.cuda.current_stream()
                 here.wait_stream(torch.cuda.ExternalStream(ent[1]) if ent[1] else torch.cuda.default_stream())
@@ -969,7 +1012,8 @@ class _ConvBase(nn.Module):
             c1, c2 = x.parts[0].shape[1], (x.parts[1].shape[1] if len(x.parts) > 1 else 0)
             edges = cm.batch_offsets(src)
             padded = [_pad_plan(c1, c2, self.out_channels, b - a) is not None for a, b in zip(edges[:-1], edges[1:]) if b > a]
-            if any(padded) and not all(padded):
+            if any(padded) and not all(padded) and not _narrow_bf16('k3' if self.ks == 3 else 'k1', c1, c2, self.out_channels):
+                # (a narrow bf16 layer has ONE form on every map, below PAD_MIN_ROWS too)
                 big = self._forward_fused(x, cm, src, coordinates, act, clip, PAD_MIN_ROWS).F
                 small = self._forward_fused(x, cm, src, coordinates, act, clip, 0).F
                 out = torch.empty_like(small)
@@ -1038,6 +1082,25 @@ class _ConvBase(nn.Module):
             t._bf16 = [(comp, ops._stream())]
         return t
 
+    def _forward_bf16_narrow(self, x: SparseTensor, cm: CoordinateManager, src: _Map, ep: dict) -> SparseTensor:
+        """a 3x3x3 layer of the narrow set on fpcc_conv_bf16_narrow (inside conv_inference_dtype(torch.bfloat16, profile=2)): the padded
+        form on every map -- parts zero-padded to whole 16-channel steps by the cast, the zero-padded weights of the fp32 'pad' form
+        packed once, the layer's own columns out; the row order as that form chooses it, the table indexed by output row"""
+        xb = x.bf16_parts(pad16=True)
+        x1, x2 = xb[0], (xb[1] if len(xb) > 1 else None)
+        c1, c2 = x.parts[0].shape[1], (x.parts[1].shape[1] if len(x.parts) > 1 else 0)
+        c1p, c2p = x1.shape[1], (0 if x2 is None else x2.shape[1])
+        wp, _ = self._padded_weights(c1, c2, (c1p, c2p, 32))
+        ro = cm._row_order(src) if c1p + c2p > 16 else None       # 16 channels: one gather per neighbour, Morton locality wins
+        res = ops.conv_bf16_narrow(x1, ops.packed_weights_bf16(wp, 27, c1p + c2p, 32), self.out_channels, src.n, x2=x2,
+                                   nbr=cm._nbr27(src), n_offsets=27, nbr_ks=src.n, nbr_os=1, row_order=ro,
+                                   out_bf16=True if self._bf16_out else None, **ep)
+        out, comp = res if isinstance(res, tuple) else (res, None)
+        t = SparseTensor(out, coordinate_map_key=src.key, coordinate_manager=cm)
+        if comp is not None:
+            t._bf16 = [(comp, ops._stream())]
+        return t
+
     def _forward_fused(self, x: SparseTensor, cm: CoordinateManager, src: _Map, coordinates: Optional[CoordinateMapKey], act: _Act,
                        clip: float, plan_rows: int) -> SparseTensor:
         """inference path: one fused launch.  plan_rows: the row count PAD_MIN_ROWS is compared with (the map's, or its clouds')"""
@@ -1051,6 +1114,8 @@ class _ConvBase(nn.Module):
         kw = dict(x2=x2, pack=True, **ep)
         kind, dst, table = self._resolve(cm, src, coordinates)
         form, shape = _layer_form(kind, c1, c2, c_out, plan_rows)
+        if _narrow_bf16(kind, c1, c2, c_out):
+            return self._forward_bf16_narrow(x, cm, src, ep)
         if inference_dtype() is torch.bfloat16 and ops.bf16_inference_eligible(kind, c1, c2, c_out) and \
                 (self.GENERATIVE or kind != 'gen' or c_out >= 32):
             # (the last clause: a TRANSPOSED module onto a generated map has no side-by-side weights -- the exception _layer_form
@@ -1118,11 +1183,13 @@ class MinkowskiConvolution(_ConvBase):
     pass
 
 
-def mark_bf16_producers(model: nn.Module) -> int:
+def mark_bf16_producers(model: nn.Module, profile: int = 1) -> int:
     """For a model that is going to run inside conv_inference_dtype(torch.bfloat16): wherever two convolution blocks follow each other in an
     nn.Sequential and the second is a bf16-eligible single-source layer, the first is asked to write the bf16 companion of its output
     (if it runs on the bf16 entry itself), which saves the consumer's cast.  Changes no result -- the companion equals the cast bit for
-    bit -- and nothing outside the context.  -> the number of layers marked"""
+    bit -- and nothing outside the context.  profile: the one the model will run under (2 also marks the producers of narrow
+    consumers; a companion serves a narrow consumer only when its width is a whole number of 16-channel steps).
+    -> the number of layers marked"""
     marked = 0
     for seq in model.modules():
         if not isinstance(seq, nn.Sequential):
@@ -1136,7 +1203,8 @@ def mark_bf16_producers(model: nn.Module) -> int:
             if act is not None and not isinstance(act, (MinkowskiPReLU, MinkowskiReLU)):
                 continue                                  # an unfused activation makes a new tensor: the companion would be dropped
             kind = 'gen' if cb.GENERATIVE else 'k2s2T' if cb.TRANSPOSED else {1: 'k1', 3: 'k3'}.get(cb.ks, 'k2s2')
-            if ca.out_channels == cb.in_channels and ops.bf16_inference_eligible(kind, cb.in_channels, 0, cb.out_channels):
+            if ca.out_channels == cb.in_channels and ops.bf16_profile_eligible(kind, cb.in_channels, 0, cb.out_channels, profile) and \
+                    (ca.out_channels % 16 == 0 or not ops.bf16_narrow_eligible(kind, cb.in_channels, 0, cb.out_channels)):
                 ca._bf16_out = True
                 marked += 1
     return marked

@@ -160,6 +160,10 @@ _SIGS = {
     'fpcc_conv_bf16_fused': (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _i64,
                                     _vp, _i64, _vp, _i64, _i64, _i32, _vp, _f32, _vp, _vp]),
     'fpcc_conv_bf16_fused_launches': (_i64, []),
+    'fpcc_conv_bf16_narrow': (_i32, [_vp, _i32, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _i64,
+                                     _vp, _i64, _vp, _i64, _i64, _i32, _vp, _f32, _vp, _vp]),
+    'fpcc_conv_bf16_narrow_launches': (_i64, []),
+    'fpcc_cast_pad_f32_bf16': (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
 }
 HIP_SYMBOLS = tuple(_SIGS) + ('fpcc_last_error',)
 _BLOCKING_ENTRY_POINTS = ('fpcc_hilbert3d_encode', 'fpcc_conv_debug_stamps', 'fpcc_conv_i8_debug_stamps', 'fpcc_int_init')
@@ -1268,8 +1272,18 @@ def _rows2d_bf16(t: torch.Tensor, name: str):
     return t.data_ptr(), t.shape[1], (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0)))
 
 
-def cast_bf16(x: torch.Tensor) -> torch.Tensor:
-    """fp32 rows (any row pitch of whole 16-byte pieces) -> a packed bfloat16 matrix, round to nearest even (fpcc_cast_f32_bf16)"""
+def cast_bf16(x: torch.Tensor, pad16: bool = False) -> torch.Tensor:
+    """fp32 rows (any row pitch of whole 16-byte pieces) -> a packed bfloat16 matrix, round to nearest even (fpcc_cast_f32_bf16).
+    pad16: rows of ANY width and pitch -> a packed matrix of the width rounded up to 16, padding columns zero (fpcc_cast_pad_f32_bf16)"""
+    if pad16:
+        if x.dim() != 2 or x.dtype != torch.float32 or not x.is_cuda or (x.shape[1] > 1 and x.stride(1) != 1) or x.shape[1] < 1:
+            raise TypeError('x must be a 2-D float32 GPU tensor with unit column stride')
+        n, c = x.shape
+        ld = x.stride(0) if n > 1 else max(c, x.stride(0))
+        cp = (c + 15) // 16 * 16
+        out = torch.empty((n, cp), dtype=torch.bfloat16, device=x.device)
+        _ok(lib().fpcc_cast_pad_f32_bf16(x.data_ptr(), ld, n, c, out.data_ptr(), cp, _stream()))
+        return out
     p, c, ld = _rows2d(x, 'x')
     n = x.shape[0]
     out = torch.empty((n, c), dtype=torch.bfloat16, device=x.device)
@@ -1324,6 +1338,32 @@ _BF16_KINDS = ('k1', 'k3', 'k2s2', 'k2s2T', 'gen')
 _BF16_REMOVED = frozenset({('gen', 128, 0, 32), ('k2s2', 128, 0, 128), ('k2s2T', 128, 0, 128), ('k1', 64, 0, 32), ('k1', 128, 0, 64)})
 
 
+# Profile 2: profile 1 plus the NARROW set, the 3x3x3 layers whose padded shape fpcc_conv_bf16_narrow takes (conv_bf16_narrow.hip).
+# The geometry+colour codec's inference_dtype = 'bfloat16' runs under it; lossy_coord_v2 stays on profile 1, whose set is frozen.
+FPCC_BF16_PROFILE_COLOR = 2
+# Narrow shapes taken out of profile 2 by the same keep rule, summed over compress + decompress of the benchmark's colour frame
+# (profiles/infer_bf16_color.md).  (kind, c1, c2, c_out), the layer's counts
+_BF16_REMOVED_COLOR = frozenset({('k3', 1, 0, 1)})
+
+
+def _ceil16(c: int) -> int:
+    return (int(c) + 15) // 16 * 16
+
+
+def bf16_narrow_eligible(kind: str, c1: int, c2: int, c_out: int) -> bool:
+    """the narrow set of profile 2: a 'k3' layer of 1..32 output columns whose sources, each rounded up to 16 channels, are 16, 32 or 48
+    (+ 0 or 16) wide with at most 64 together -- less the layers of profile 1, the 'split' shape (c_out == 1, one source of whole
+    16-channel steps: it keeps its fp32 form) and _BF16_REMOVED_COLOR.  A pure function of the kind and the channel counts."""
+    if kind != 'k3' or c1 < 1 or c2 < 0 or not 1 <= c_out <= 32:
+        return False
+    p1, p2 = _ceil16(c1), _ceil16(c2)
+    if p1 not in (16, 32, 48) or p2 not in (0, 16) or p1 + p2 > 64:
+        return False
+    if bf16_inference_eligible(kind, c1, c2, c_out) or (c_out == 1 and c2 == 0 and c1 % 16 == 0):
+        return False
+    return (kind, c1, c2, c_out) not in _BF16_REMOVED_COLOR
+
+
 def bf16_inference_eligible(kind: str, c1: int, c2: int, c_out: int) -> bool:
     """Whether a _ConvBase layer of this kind ('k1' | 'k3' | 'k2s2' | 'k2s2T' | 'gen') and these channel counts (c1 + c2 in, c_out out,
     the LAYER's counts) runs on fpcc_conv_bf16_fused inside engine.conv_inference_dtype(torch.bfloat16).  A pure function of the kind
@@ -1335,12 +1375,24 @@ def bf16_inference_eligible(kind: str, c1: int, c2: int, c_out: int) -> bool:
     ONE exception lives at the call site (engine._ConvBase._forward_fused), because it is a property of the module class and not of
     these four arguments: kind 'gen' is also what a TRANSPOSED module onto a generated map resolves to, and such a module has no
     side-by-side weights -- it is the groups = 8 launch, which needs c_out >= 32.  With c_out in {4, 8, 16} this function says True
-    (the generative module's packed form) and that module stays fp32.  No shipped configuration has such a layer."""
+    (the generative module's packed form) and that module stays fp32.  No shipped configuration has such a layer.
+    This is PROFILE 1 (FPCC_BF16_PROFILE_VERSION); bf16_profile_eligible answers for either profile."""
     if kind not in _BF16_KINDS or c1 < 32 or c1 % 32 or c2 < 0 or c2 % 32 or (kind, c1, c2, c_out) in _BF16_REMOVED:
         return False
     if kind == 'gen' and c2 == 0 and 8 * c_out in (32, 64, 128, 256):
         return True
     return c_out in (32, 64, 128, 256)
+
+
+def bf16_profile_eligible(kind: str, c1: int, c2: int, c_out: int, profile: int = 1) -> bool:
+    """Whether the layer runs in bf16 inside engine.conv_inference_dtype(torch.bfloat16, profile=profile): profile 1
+    (FPCC_BF16_PROFILE_VERSION) is bf16_inference_eligible and nothing else; profile 2 (FPCC_BF16_PROFILE_COLOR) adds the layers of
+    bf16_narrow_eligible, which go to fpcc_conv_bf16_narrow.  Like both, a pure function of the kind and the channel counts."""
+    if profile not in (FPCC_BF16_PROFILE_VERSION, FPCC_BF16_PROFILE_COLOR):
+        raise ValueError(f'unknown bfloat16 inference profile {profile!r}')
+    if profile == FPCC_BF16_PROFILE_COLOR and bf16_narrow_eligible(kind, c1, c2, c_out):
+        return True
+    return bf16_inference_eligible(kind, c1, c2, c_out)
 
 
 def conv_bf16_fused_launches() -> int:
@@ -1400,6 +1452,47 @@ def conv_bf16_fused(x1: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out:
             po, ldo, pb, ldb, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
             _dev(row_order, torch.int32, 'row_order', True), _stream())
     _untraced_launch(fn, call)              # (not listed in a conv trace: tools/infer_bf16_ab.py times these layers at the engine's call)
+    return out if comp is None else (out, comp)
+
+
+def conv_bf16_narrow_launches() -> int:
+    """launches of fpcc_conv_bf16_narrow by this process so far"""
+    return int(lib().fpcc_conv_bf16_narrow_launches())
+
+
+def conv_bf16_narrow(x1: torch.Tensor, w_packed: torch.Tensor, c_out: int, n_out: int, *, x2: Optional[torch.Tensor] = None,
+                     nbr: Optional[torch.Tensor] = None, n_offsets: int = 1, nbr_ks: int = 0, nbr_os: int = 1,
+                     bias: Optional[torch.Tensor] = None, groups: int = 1, out_map: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, act: int = ACT_NONE, slope: Optional[torch.Tensor] = None, clip: float = 0.0,
+                     row_order: Optional[torch.Tensor] = None, out_bf16=None):
+    """conv_bf16_fused for narrow layers: x1 of 16, 32 or 48 bfloat16 channels, x2 of 16 or none, 1 <= c_out <= 32 columns stored;
+    w_packed the image of the weights zero-padded to [n_offsets, c1 + c2, 32]; see fpcc_conv_bf16_narrow.  out / out_bf16 are
+    c_out wide (windows of wider matrices are fine).  -> out, or (out, companion) when out_bf16 is given"""
+    p1, c1, ld1 = _rows2d_bf16(x1, 'x1')
+    if x2 is not None:
+        p2, c2, ld2 = _rows2d_bf16(x2, 'x2')
+    else:
+        p2, c2, ld2 = None, 0, 0
+    if w_packed.dtype != torch.bfloat16 or not w_packed.is_cuda or not w_packed.is_contiguous() or \
+            w_packed.numel() != n_offsets * (c1 + c2) * 32:
+        raise ValueError(f'packed weights must hold {n_offsets} x {c1 + c2} x 32 bfloat16')
+    if bias is not None and bias.numel() != c_out:
+        raise ValueError(f'bias must hold {c_out} values')
+    out, po, ldo, _ = _conv_out(out, None, n_out, 1, c_out, 0, x1.device)
+    if out.shape[0] < n_out:
+        raise ValueError('output has fewer rows than n_out')
+    comp, pb, ldb = None, None, 0
+    if out_bf16 is not None and out_bf16 is not False:
+        comp = torch.empty((out.shape[0], c_out), dtype=torch.bfloat16, device=x1.device) if out_bf16 is True else out_bf16
+        pb, cb, ldb = _rows2d_bf16(comp, 'out_bf16')
+        if cb != c_out or comp.shape[0] != out.shape[0]:
+            raise ValueError('bf16 companion shape mismatch')
+    fn = lib().fpcc_conv_bf16_narrow
+    call = (p1, c1, ld1, p2, c2, ld2, _dev(nbr, torch.int32, 'nbr', True), n_offsets, nbr_ks, nbr_os, w_packed.data_ptr(),
+            _dev(bias, torch.float32, 'bias', True), c_out, groups, _dev(out_map, torch.int32, 'out_map', True), 1, 1,
+            po, ldo, pb, ldb, n_out, act, _dev(slope, torch.float32, 'slope', True), float(clip),
+            _dev(row_order, torch.int32, 'row_order', True), _stream())
+    _untraced_launch(fn, call)
     return out if comp is None else (out, comp)
 
 

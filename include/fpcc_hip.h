@@ -1048,6 +1048,27 @@ int fpcc_conv_bf16_fused(const uint16_t *x1, int c1, int64_t ld1, const uint16_t
                          int act, const float *slope, float clip, const int32_t *row_order, void *stream);
 long long fpcc_conv_bf16_fused_launches(void);
 
+/* bfloat16 inference, narrow layers (conv_bf16_narrow.hip): fpcc_conv_bf16_fused for c1 in {16, 32, 48}, c2 in {0, 16},
+ * c1 + c2 <= 64, 1 <= c_out <= 32, groups == 1 and no out_map (both refused otherwise); the other arguments as there.
+ *   w_packed      the image fpcc_conv_pack_weights_bf16 makes of the n_offsets matrices zero-padded to [c1 + c2][32];
+ *   bias          c_out floats, or NULL;
+ *   out, out_bf16 columns < c_out are stored and no others: pitches ldo, ldb >= c_out.
+ * Same lane maps and summation chain, so the fp32 output is bit for bit fpcc_conv_bf16_fused's on the same operands zero-padded to
+ * that entry's shape (x1 or x2 to 32 channels, weights and bias to 32 columns), columns < c_out.  What differs is the gather: the A
+ * fragments of a wave's whole chain (at most 8 offsets of 1..4 K steps, 16 bytes per lane and step) are requested together.
+ * These bits are part of the stream format of a codec run under FPCC_BF16_PROFILE_COLOR of hipops.py, and of no other stream.
+ * fpcc_conv_bf16_narrow_launches: diagnostics, launches of this entry by this process so far. */
+int fpcc_conv_bf16_narrow(const uint16_t *x1, int c1, int64_t ld1, const uint16_t *x2, int c2, int64_t ld2,
+                          const int32_t *nbr, int n_offsets, int64_t nbr_ks, int64_t nbr_os,
+                          const uint16_t *w_packed, const float *bias, int c_out, int groups,
+                          const int32_t *out_map, int64_t om_os, int64_t om_gs,
+                          float *out, int64_t ldo, uint16_t *out_bf16, int64_t ldb, int64_t n_out,
+                          int act, const float *slope, float clip, const int32_t *row_order, void *stream);
+long long fpcc_conv_bf16_narrow_launches(void);
+/* dst[r][0..ceil16(c)) = bf16(src[r][0..c)) followed by zeros, r < n, round to nearest even.  Any c >= 1 and any ld >= c (floats, source
+ * 4-byte aligned); ldd (bf16) >= ceil16(c) and a multiple of 8, dst 16-byte aligned. */
+int fpcc_cast_pad_f32_bf16(const float *src, int64_t ld, int64_t n, int c, uint16_t *dst, int64_t ldd, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
