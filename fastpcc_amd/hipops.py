@@ -164,6 +164,8 @@ _SIGS = {
                                      _vp, _i64, _vp, _i64, _i64, _i32, _vp, _f32, _vp, _vp]),
     'fpcc_conv_bf16_narrow_launches': (_i64, []),
     'fpcc_cast_pad_f32_bf16': (_i32, [_vp, _i64, _i64, _i32, _vp, _i64, _vp]),
+    'fpcc_mt_table_build': (_i64, [_vp, _vp, _vp, _i64, _vp, _i64]),
+    'fpcc_mt_lerp_f32': (_i32, [_vp, _i64, _i64, _f32, _vp]),
 }
 HIP_SYMBOLS = tuple(_SIGS) + ('fpcc_last_error',)
 _BLOCKING_ENTRY_POINTS = ('fpcc_hilbert3d_encode', 'fpcc_conv_debug_stamps', 'fpcc_conv_i8_debug_stamps', 'fpcc_int_init')
@@ -2345,3 +2347,72 @@ def rans_rows_il_decode_dev(blocks: torch.Tensor, chunks: torch.Tensor, rows: to
         raise ValueError('symbols_out must hold one symbol per row')
     _dev(sym, torch.int16, 'symbols_out', n == 0)
     return _il_decode_dev(lib().fpcc_rans_rows_il_decode_dev, blocks, chunks, rows, 'rows', n, (int(c),), sym, n_seg)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# multi-tensor lerp (the weight average of the training driver)
+
+MT_CHUNK = 4096                     # FPCC_MT_CHUNK of include/fpcc_hip.h
+_MT_HEADER_WORDS = 4                # fpcc_mt_header: magic, n_entries, n_chunks, n_elements
+_MT_MAGIC = 0x3130544d43435046      # "FPCCMT01": the image layout of multi_tensor.hip
+
+
+def mt_table_image(dst_ptrs: Sequence[int], src_ptrs: Sequence[int], counts: Sequence[int], table_bytes: Optional[int] = None):
+    """the host image of a lerp table over raw device addresses (fpcc_mt_table_build; no GPU needed): -> (image: int64 CPU tensor,
+    n_entries, n_chunks, n_elements).  Raises FpccError for what the library refuses: n < 0, a null address with n > 0, an address
+    that is not 4-byte aligned, overlapping dst / src ranges, and -- with `table_bytes` given -- an image buffer that is too small"""
+    k = len(counts)
+    if not (len(dst_ptrs) == len(src_ptrs) == k):
+        raise ValueError('dst_ptrs, src_ptrs and counts must have one item per entry')
+    dst = (_vp * max(k, 1))(*[int(p) or None for p in dst_ptrs])
+    src = (_vp * max(k, 1))(*[int(p) or None for p in src_ptrs])
+    cnt = (_i64 * max(k, 1))(*[int(c) for c in counts])
+    L = lib()
+    need = _ok(L.fpcc_mt_table_build(dst, src, cnt, k, None, 0))
+    size = need if table_bytes is None else int(table_bytes)
+    image = torch.zeros(max((size + 7) // 8, 1), dtype=torch.int64)
+    _ok(L.fpcc_mt_table_build(dst, src, cnt, k, image.data_ptr(), size))
+    magic, n_entries, n_chunks, n_elements = image[:_MT_HEADER_WORDS].tolist()
+    # the kernel checks nothing, so the header is checked here, while the image is still on the host: the layout this module was
+    # written for, and counts that agree with what was asked for
+    if magic != _MT_MAGIC or n_entries != k or n_elements != sum(int(c) for c in counts) or \
+            size < 8 * _MT_HEADER_WORDS + 24 * n_entries + 16 * n_chunks:
+        raise FpccError(f'mt_table_image: header {magic:#x}, {n_entries} entries, {n_chunks} chunks, {n_elements} elements does not '
+                        f'describe the {k} entries asked for')
+    return image, n_entries, n_chunks, n_elements
+
+
+class MtTable:
+    """Descriptor table of mt_lerp: pairs (dst, src) of contiguous fp32 GPU tensors of equal size on one device, validated by the
+    library and uploaded once.  Holds the tensors, so the memory the table names stays allocated for as long as the table lives;
+    `ptrs` are the addresses it was built from (dst entries, then src entries).  Whether a MODULE still keeps its parameters at these
+    addresses is for the owner of the module to ask (fastpcc_amd/model_ema.py compares before every launch)."""
+
+    def __init__(self, dst_tensors: Sequence[torch.Tensor], src_tensors: Sequence[torch.Tensor]):
+        self.dst, self.src = list(dst_tensors), list(src_tensors)
+        if len(self.dst) != len(self.src):
+            raise ValueError('one src per dst')
+        self.device = None
+        for i, (d, s) in enumerate(zip(self.dst, self.src)):
+            _dev(d, torch.float32, f'dst[{i}]')
+            _dev(s, torch.float32, f'src[{i}]')
+            if d.numel() != s.numel():
+                raise ValueError(f'entry {i}: dst has {d.numel()} elements, src {s.numel()}')
+            if self.device is None:
+                self.device = d.device
+            if d.device != self.device or s.device != self.device:
+                raise ValueError(f'entry {i}: every tensor of a table must live on {self.device}')
+        self.ptrs = tuple([t.data_ptr() for t in self.dst] + [t.data_ptr() for t in self.src])
+        k = len(self.dst)
+        image, self.n_entries, self.n_chunks, self.n_elements = mt_table_image(self.ptrs[:k], self.ptrs[k:], [d.numel() for d in self.dst])
+        self.image = None if self.device is None else image.to(self.device)
+
+
+def mt_lerp(table: MtTable, weight: float) -> None:
+    """dst = lerp(dst, src, weight) for every entry of `table`, in place, in one launch on torch's current stream (fpcc_mt_lerp_f32:
+    torch.lerp's two-sided fp32 form; weight 1 copies bit for bit, weight 0 launches nothing).  The kernel writes through raw
+    addresses: the tensors' `_version` counters do not move (fastpcc_amd/model_ema.py, ModelEma.refresh)."""
+    if table.n_chunks == 0:
+        return
+    with torch.cuda.device(table.device):
+        _ok(lib().fpcc_mt_lerp_f32(table.image.data_ptr(), table.n_entries, table.n_chunks, float(weight), _stream()))

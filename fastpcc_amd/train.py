@@ -1,8 +1,9 @@
 """Data-parallel training of the codecs: one process per GPU, gradients all-reduced over RCCL (torch.distributed backend
 'nccl' on ROCm) by DistributedDataParallel.  The role of /root/reference/train.py:195-222,262-420 for this path -- DDP
 wrapping (with the non-tensor `_extra_state` entries kept out of DDP's broadcast, train.py:204-214), parameter groups
-by `Model.params_divider`, AdamW + StepLR per group, gradient accumulation under `no_sync`, gradient clipping -- without
-the reference's dataset / logging / checkpoint shell, which is out of scope.
+by `Model.params_divider`, AdamW + StepLR per group, gradient accumulation under `no_sync`, gradient clipping, the weight average
+(fastpcc_amd/model_ema.py) after each update.  The shell around it -- datasets, epochs, checkpoints, resume, the periodic test,
+logging: train.py:139-484 -- is fastpcc_amd/run_train.py.
 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench_train.py --gpus N --steps K --warmup W
@@ -111,8 +112,9 @@ def build_optimizers(model: torch.nn.Module, cfg: TrainConfig):
 class Trainer:
     """model(batch) must return a dict with a differentiable 'loss' (PCC.forward in train mode)"""
 
-    def __init__(self, model: torch.nn.Module, cfg: TrainConfig, device: torch.device):
-        self.cfg, self.device = cfg, device
+    def __init__(self, model: torch.nn.Module, cfg: TrainConfig, device: torch.device, ema=None):
+        """ema: a fastpcc_amd.model_ema.ModelEma updated after every optimiser step (train.py:403-404), or None"""
+        self.cfg, self.device, self.ema = cfg, device, ema
         self.model = wrap_ddp(model.to(device).train(), cfg, device)
         self.optimizers, self.schedulers = build_optimizers(self.model, cfg)
         self.micro_step = 0
@@ -142,6 +144,8 @@ class Trainer:
                 if opt is not None:
                     opt.zero_grad(set_to_none=True)
             refresh_prelu_cache(unwrap(self.model))       # host copy of the PReLU slopes' signs for the fused training node
+            if self.ema is not None:                      # step read before micro_step moves: global_step // grad_acc_steps
+                self.ema.update(unwrap(self.model), step=self.optimisation_step)
         self.micro_step += 1
         # one read-back for every logged term, after the whole step has been queued
         keys = list(out)

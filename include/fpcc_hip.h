@@ -1069,6 +1069,36 @@ long long fpcc_conv_bf16_narrow_launches(void);
  * 4-byte aligned); ldd (bf16) >= ceil16(c) and a multiple of 8, dst 16-byte aligned. */
 int fpcc_cast_pad_f32_bf16(const float *src, int64_t ld, int64_t n, int c, uint16_t *dst, int64_t ldd, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------------ */
+/* Multi-tensor in-place lerp (multi_tensor.hip): the weight average of the training driver in ONE launch.        */
+/* Replaces the per-step torch._foreach_lerp_ over two state_dict() walks of lib/model_ema.py:92-108.              */
+/* ------------------------------------------------------------------------------------------------------------ */
+#define FPCC_MT_CHUNK 4096            /* elements of one unit of work */
+typedef struct { float *dst; const float *src; int64_t n; } fpcc_mt_entry;
+typedef struct { int64_t magic, n_entries, n_chunks, n_elements; } fpcc_mt_header;
+/* Builds, ON THE HOST, the table image the kernel reads: fpcc_mt_header, n_entries fpcc_mt_entry, then one 16-byte record per chunk
+ * (entry, first element, count <= FPCC_MT_CHUNK; entries in order, chunks of an entry ascending).  The header is for the HOST side of
+ * the caller: magic ("FPCCMT01", this layout) and n_elements (the sum of n) let it check, before the upload, that the image describes
+ * what it asked for (hipops.mt_table_image does); n_entries and n_chunks are what it hands to fpcc_mt_lerp_f32.  The device reads
+ * neither.  dst_host / src_host / n_host are HOST
+ * arrays of n_entries DEVICE addresses and element counts; nothing is dereferenced on the device side and no HIP call is made, so this
+ * runs without a GPU.  table_host == NULL returns the image size in bytes; otherwise the image is written to table_host (8-byte aligned,
+ * table_bytes >= that size, else FPCC_E_WORKSPACE) and its size returned; the caller copies it to device memory.  Refused with
+ * FPCC_E_ARG, before anything is written: n < 0, a null address with n > 0, an address that is not 4-byte aligned, an entry whose
+ * dst and src ranges overlap.  Entries with n == 0 get no chunk.  Ranges of DIFFERENT entries are the caller's business. */
+int64_t fpcc_mt_table_build(const void *const *dst_host, const void *const *src_host, const int64_t *n_host, int64_t n_entries,
+                            void *table_host, int64_t table_bytes);
+/* dst = lerp(dst, src, weight) for every entry of a table image in device memory (n_entries, n_chunks: its header's), fp32, one
+ * launch of min(n_chunks, 2048) blocks of 256 threads that walk the chunks grid-stride.  Per element, with d = dst, s = src:
+ *      weight <  0.5     d = fmaf(weight, s - d, d)
+ *      weight >= 0.5     d = fmaf(-(1 - weight), s - d, s)           (torch.lerp's two-sided form; 1 - weight is exact there)
+ *      weight == 1       d = s, a plain copy: bit-exact for every value, non-finite ones included
+ *      weight == 0       nothing is launched.
+ * An entry whose dst and src are both 16-byte aligned moves 16 bytes per lane with a scalar tail; any other entry 4 bytes per lane.
+ * weight outside [0, 1] (NaN included) is refused.  The table must be the unmodified image of fpcc_mt_table_build and the memory it
+ * names must be live: the kernel checks nothing. */
+int fpcc_mt_lerp_f32(const void *table, int64_t n_entries, int64_t n_chunks, float weight, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
